@@ -2,7 +2,13 @@
 """Benchmark: batched OSC control steps/s on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N --steps K --warmup W] [--robot unitree_go2] [--nenv-per-gpu 4096]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds every
+other measurement beside it (host_fed, north_star, mixed, the per-kernel roofline objects, hbm_inputs,
+warm, front_end, pipeline, single_env, cpu_baseline).  --dump-outputs DIR writes what the last timed
+step computed (tau, status, iters) as DIR/<name>.npy.
 
 One "step" = one pass of the hot path over one batch: for every environment the QP assembly
 + QP solve + torque slice (the reference's update_optimization_data + update_optimization +
@@ -223,7 +229,7 @@ def tumbling_pipeline(solver, nenv: int, steps: int, warmup: int, seed: int, str
 
 
 def run_mixed(args, world, rank, dev, barrier, solver_cls=None, multi_fn=None,
-              nenv=None) -> dict | None:
+              nenv=None, dump=None) -> dict | None:
     """BASELINE configs[4]: mixed Go2 + WaLTER Sr.  Every rank solves its own shard of `nenv`
     Go2 envs AND `nenv` WaLTER envs (4,096 + 4,096 per GPU: 65,536 over 8 GPUs) in ONE
     osc_batch_solve_multi call: one assembly grid and one interior-point grid for both models,
@@ -275,6 +281,8 @@ def run_mixed(args, world, rank, dev, barrier, solver_cls=None, multi_fn=None,
     clock.sync()
     barrier()
     elapsed = time.perf_counter() - t0
+    if dump:
+        dump_outputs(dump, rank, {f"{s.robot}_": o for s, _, o in jobs})
     kernel_ms = e0.elapsed_time(e1) / args.steps
     conv = sum(int((o.status == 0).sum().item()) for _, _, o in jobs)
     stats = reduce_stats(world, dev, 2 * nenv, elapsed, kernel_ms, 0.0, conv)
@@ -577,11 +585,57 @@ class DeviceClock:
         return torch.cuda.current_stream(self.dev) if self.cuda else None
 
 
+DUMP_MAX_BYTES = 64 << 20
+CLOCK_RAMP_S = 0.5
+
+
+def dump_outputs(path: str, rank: int, outs: dict) -> None:
+    """--dump-outputs: the timed path's outputs after its last timed step, as the caller of
+    solve_into receives them (`outs`: name -> SolveResult), one float64 .npy per array: <name>.npy
+    on rank 0, <name>.rank<r>.npy on the others.  Past DUMP_MAX_BYTES in all, a fixed seeded sample
+    of the envs (the same rows of every array; their indices in <name>env_index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+    per_env = sum(8 * (r.tau.shape[1] + 3) for r in outs.values())
+    keep = DUMP_MAX_BYTES // max(per_env, 1)
+    for name, r in outs.items():
+        arrays = {k: getattr(r, k).detach().cpu().numpy().astype(np.float64)
+                  for k in ("tau", "status", "iters")}
+        nenv = arrays["tau"].shape[0]
+        if nenv > keep:
+            idx = np.sort(np.random.default_rng(20240531).choice(nenv, size=keep, replace=False))
+            arrays = {k: a[idx] for k, a in arrays.items()}
+            arrays["env_index"] = idx.astype(np.float64)
+        for k, a in arrays.items():
+            np.save(os.path.join(path, f"{name}{k}{sfx}.npy"), a)
+
+
+def clock_ramp(solver, out, inputs, clock, seconds: float = CLOCK_RAMP_S) -> None:
+    """Part of a plain run's set-up: the headline's own solves, untimed, for `seconds`, so that its
+    timed steps start at the clocks of a running control loop rather than on an idle GPU's ramp
+    (what the host_fed / north_star / mixed lines do for the headline of a --full run)."""
+    if not clock.cuda:
+        return
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(50):
+            solver.solve_into(out, *inputs)
+        clock.sync()
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything reported beside the headline (host_fed, "
+                         "north_star, mixed, the per-kernel roofline objects, hbm_inputs, warm, "
+                         "front_end, pipeline, single_env, cpu_baseline; each has its own --no-* "
+                         "switch); off: the headline's set-up, warmup and timed steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (tau, status, "
+                         "iters of every env of this rank) as DIR/<name>.npy in float64")
     ap.add_argument("--robot", default="unitree_go2")
     ap.add_argument("--nenv-per-gpu", type=int, default=4096)
     ap.add_argument("--scenario", default="standing", choices=["standing", "tumbling"])
@@ -714,33 +768,59 @@ def run_headline(args, world: int, rank: int, dev: torch.device, barrier, solver
     clock.sync()
     barrier()
     elapsed = time.perf_counter() - t0
-    every = max(1, args.event_every)
-    nsample = max(4, args.steps // every)
-    ev = [[clock.event() for _ in range(3)] for _ in range(nsample)]
-    for k in range(nsample):
-        mask = masks[k % len(masks)]
-        ev[k][0].record(stream)
-        solver.assemble_into(out, *inputs[:5], mask)
-        ev[k][1].record(stream)
-        solver.solve_assembled_into(out, mask)
-        ev[k][2].record(stream)
-        if k + 1 < nsample:   # (bare steps between the sampled ones: the loop's steady state)
-            for j in range(every - 1):
-                mj = masks[(k + 1 + j) % len(masks)]
-                solver.assemble_into(out, *inputs[:5], mj)
-                solver.solve_assembled_into(out, mj)
-    clock.sync()
-    setup_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / len(ev)
-    ipm_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / len(ev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"": out})
+    setup_ms = ipm_ms = 0.0
+    if args.full:
+        every = max(1, args.event_every)
+        nsample = max(4, args.steps // every)
+        ev = [[clock.event() for _ in range(3)] for _ in range(nsample)]
+        for k in range(nsample):
+            mask = masks[k % len(masks)]
+            ev[k][0].record(stream)
+            solver.assemble_into(out, *inputs[:5], mask)
+            ev[k][1].record(stream)
+            solver.solve_assembled_into(out, mask)
+            ev[k][2].record(stream)
+            if k + 1 < nsample:   # (bare steps between the sampled ones: the loop's steady state)
+                for j in range(every - 1):
+                    mj = masks[(k + 1 + j) % len(masks)]
+                    solver.assemble_into(out, *inputs[:5], mj)
+                    solver.solve_assembled_into(out, mj)
+        clock.sync()
+        setup_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / len(ev)
+        ipm_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / len(ev)
 
     st = out.status.cpu().numpy()
-    mean_iters = float(out.iters.double().mean().item())
     stats = reduce_stats(world, dev, nenv, elapsed, setup_ms, ipm_ms, int((st == 0).sum()))
     elapsed, kernel_ms, setup_ms, ipm_ms = stats.elapsed_s, stats.kernel_ms, stats.setup_ms, stats.ipm_ms
     if rank != 0:
         return None, solver, inputs
     total = stats.total_envs
     value = job_value(stats, args.steps)
+    line = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "solves/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (seeded post-kinematics M, C, J, b, T, mask; osc_amd.synth)",
+        "config": {"workload": f"{args.robot} {args.scenario} mask={args.mask}"
+                               f"{f' redrawn per step ({args.mask_redraw} masks)' if args.mask_redraw else ''}, "
+                               f"{nenv} envs per GPU{baseline_config_tag(args, nenv)}",
+                   "robot": args.robot, "envs_per_gpu": nenv, "global_envs": total,
+                   "parallelism": f"env-shard x{world}"},
+        "converged_frac": stats.converged,
+    }
+    if not args.full:   # (the roofline objects need the sampled run's per-kernel durations)
+        return line, solver, inputs
+    mean_iters = float(out.iters.double().mean().item())
     bps = bytes_per_solve(args.robot)
     # dominant kernel = osc_ipm_kernel (~80 % of the solve): path bytes per launch over its
     # own event-timed duration; the setup + IPM pair is reported beside it
@@ -761,24 +841,7 @@ def run_headline(args, world: int, rank: int, dev: torch.device, barrier, solver
     flops = algorithmic_flops(args.robot, mean_iters)
     tflops = flops * nenv / (kernel_ms * 1e-3) / 1e12
     ipm_name = ipm_kernel_name(args.robot, nenv, dev)
-    line = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "solves/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (seeded post-kinematics M, C, J, b, T, mask; osc_amd.synth)",
-        "config": {"workload": f"{args.robot} {args.scenario} mask={args.mask}"
-                               f"{f' redrawn per step ({args.mask_redraw} masks)' if args.mask_redraw else ''}, "
-                               f"{nenv} envs per GPU{baseline_config_tag(args, nenv)}",
-                   "robot": args.robot, "envs_per_gpu": nenv, "global_envs": total,
-                   "parallelism": f"env-shard x{world}"},
+    line.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "kernel": ipm_name, "kernel_ms": ipm_ms,
@@ -800,8 +863,7 @@ def run_headline(args, world: int, rank: int, dev: torch.device, barrier, solver
                           "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
                           "frac": tflops / FP64_PEAK_TFLOPS,
                           "flops_per_solve": flops, "mean_ipm_iters": mean_iters},
-        "converged_frac": stats.converged,
-    }
+    })
     return line, solver, inputs
 
 
@@ -951,7 +1013,7 @@ def main(argv=None) -> None:
         dist_barrier(world)
 
     if args.robot == "mixed":
-        line = run_mixed(args, world, rank, dev, barrier)
+        line = run_mixed(args, world, rank, dev, barrier, dump=args.dump_outputs)
         if line is not None:
             print(json.dumps(line), flush=True)
         if world > 1:
@@ -969,10 +1031,13 @@ def main(argv=None) -> None:
     prepared = prepare_headline(args, rank, OSCBatchSolver)
     # SURVEY.md §8(e)'s host-fed tick: every rank its own pinned feed.  It completes (synced,
     # barriers) before or after the headline's timed region -- never overlapping it
-    want_hf = bool(args.host_fed_envs.strip()) and args.robot != "mixed"
+    want_hf = args.full and bool(args.host_fed_envs.strip()) and args.robot != "mixed"
     hf = (host_fed(args, world, rank, dev, barrier, prepared[0])
           if want_hf and not args.host_fed_after else None)
-    objs = multi_gpu_objects(args, world, rank, dev, barrier, OSCBatchSolver, clock)
+    objs = (multi_gpu_objects(args, world, rank, dev, barrier, OSCBatchSolver, clock)
+            if args.full else {})
+    if not args.full:
+        clock_ramp(prepared[0], prepared[2], prepared[1], clock)
     line, solver, inputs = run_headline(args, world, rank, dev, barrier, OSCBatchSolver, clock,
                                         prepared)
     if want_hf and args.host_fed_after:
@@ -982,8 +1047,17 @@ def main(argv=None) -> None:
         if hf is not None:
             line["host_fed"] = hf
         line["clocks"] = ("the headline's timed steps run after the host_fed / north_star / mixed "
-                          "lines (GPU clocks at a running loop's level, not an idle GPU's ramp)")
-    if line is not None:
+                          "lines (GPU clocks at a running loop's level, not an idle GPU's ramp)"
+                          if args.full else
+                          f"the headline's timed steps run after {CLOCK_RAMP_S} s of the same "
+                          f"solves, untimed (GPU clocks at a running loop's level, not an idle "
+                          f"GPU's ramp)")
+    if line is not None and backend != "nccl" and world > 1:   # not a multi-GPU measurement
+        line["rehearsal"] = (f"{backend}: {world} ranks on {torch.cuda.device_count()} "
+                             f"GPU(s), ranks sharing devices")
+    if line is not None and not args.full:
+        print(json.dumps(line), flush=True)
+    elif line is not None:
         nenv = args.nenv_per_gpu
         stream = clock.stream()
         if world == 1 and args.hbm_batches > 0:
@@ -1005,9 +1079,6 @@ def main(argv=None) -> None:
             line["single_env"] = single_env(args.robot, args.single_env_ticks)
         if world == 1 and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline(args.robot, args.cpu_seconds, args.cpu_cores)
-        if backend != "nccl" and world > 1:   # not a multi-GPU measurement
-            line["rehearsal"] = (f"{backend}: {world} ranks on {torch.cuda.device_count()} "
-                                 f"GPU(s), ranks sharing devices")
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -8,9 +8,9 @@
 #   tests[=<pytest -k expr>]   GPU suite (or a selection) -> gpu_tests.log
 #   file=<tests/file.py>       one GPU test file          -> gpu_<file>.log
 #   smoke                      __graft_entry__.smoke()    -> smoke.log
-#   trace                      bench --steps 20 --warmup 5 under rocprofv3 --kernel-trace --stats
+#   trace                      bench --full --steps 20 --warmup 5 under rocprofv3 --kernel-trace --stats
 #                              -> trace20x5/, bench_20x5.json
-#   bench                      default bench (200 + 100)  -> bench_default.json
+#   bench                      bench --full (200 + 100)   -> bench_default.json
 #   bench20                    the driver's bench command -> bench_20x5_plain.json
 #   configs                    configs[2], [3], Go2 8,192 / 65,536, mixed as bench lines
 #   pmc=<robot>:<nenv>         FETCH_SIZE and WRITE_SIZE passes (separate runs) of one batch
@@ -47,9 +47,9 @@ for step in "$@"; do
     smoke)
       timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || exit $((30 + n)) ;;
     trace)
-      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/$O/trace20x5" -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 > "$O/bench_20x5.json" 2> "$O/bench_20x5.err" || exit $((30 + n)) ;;
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/$O/trace20x5" -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 > "$O/bench_20x5.json" 2> "$O/bench_20x5.err" || exit $((30 + n)) ;;
     bench)
-      timeout -k 10 400 python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err" || exit $((30 + n)) ;;
+      timeout -k 10 400 python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err" || exit $((30 + n)) ;;
     bench20)
       timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$O/bench_20x5_plain.json" 2> "$O/bench_20x5_plain.err" || exit $((30 + n)) ;;
     configs)
@@ -79,9 +79,9 @@ for step in "$@"; do
       lib=${val%%:*}; rest=${val#*:}
       AB_CONFIGS="$rest" AB_ONLY="$rest" AB_ROUNDS=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$R/$O/rocab_$n" -o run --output-format csv -- python3 tools/ab_time.py "$lib" > "$O/rocab_$n.jsonl" 2>&1 || exit $((30 + n)) ;;
     hostfed)
-      timeout -k 10 300 python bench.py --no-cpu --no-front-end --no-single-env --no-north-star --no-mixed --hbm-batches 0 --no-warm > "$O/bench_hostfed.json" 2> "$O/bench_hostfed.err" || exit $((30 + n)) ;;
+      timeout -k 10 300 python bench.py --full --no-cpu --no-front-end --no-single-env --no-north-star --no-mixed --hbm-batches 0 --no-warm > "$O/bench_hostfed.json" 2> "$O/bench_hostfed.err" || exit $((30 + n)) ;;
     rehearse)
-      OSC_DIST_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu --no-warm --no-front-end --no-single-env > "$O/rehearse_2ranks.json" 2> "$O/rehearse_2ranks.err" || exit $((30 + n)) ;;
+      OSC_DIST_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 10 --warmup 3 --full --no-cpu --no-warm --no-front-end --no-single-env > "$O/rehearse_2ranks.json" 2> "$O/rehearse_2ranks.err" || exit $((30 + n)) ;;
     py)
       # shellcheck disable=SC2086
       timeout -k 10 600 python -u $val > "$O/py_$n.log" 2>&1 || exit $((30 + n)) ;;

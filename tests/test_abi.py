@@ -14,7 +14,7 @@ from osc_qp import load_model
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADERS = [os.path.join(REPO, "include", h) for h in ("osc_batch.h", "osc_producers.h", "osc_kinematics.h",
                                                                "osc_host_feed.h")]
-REF_CONFIG = "/root/reference/config"
+REF_CONFIG = os.path.join(REPO, "tests", "golden", "reference_config")   # the reference's own files
 
 
 def test_library_loads_and_exports_header_symbols():
@@ -73,7 +73,6 @@ def test_desc_from_yaml_matches_oracle(robot):
     assert list(d.z_lb) == [-1e30, -1e30, 0.0] and list(d.z_ub) == [1e30, 1e30, 1e4]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIG), reason="reference tree not mounted")
 @pytest.mark.parametrize("robot,rel", [
     ("unitree_go2", "unitree_go2/unitree_go2_config.yaml"),
     ("walter_sr", "walter_sr/walter_sr_config.yaml"),

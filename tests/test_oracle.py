@@ -154,15 +154,13 @@ def test_reference_port_default_settings_converge():
 @pytest.mark.parametrize("robot", ["unitree_go2", "walter_sr", "walter_sr_wheels"])
 def test_closed_form_equals_literal_autogen_objective(robot):
     """build_qp's H and f against the objective written term by named term as autogen.py writes
-    it (oracle/autogen_literal.py), with the reference's own weights file when it is present:
-    the literal objective is a quadratic, so its Hessian and gradient at x = 0 follow exactly
+    it (oracle/autogen_literal.py), with the reference's own weights file (tests/golden/): the literal objective is a quadratic, so its Hessian and gradient at x = 0 follow exactly
     from values at 0, +-e_i and e_i + e_j."""
     import autogen_literal as lit
-    from osc_amd.robots import config_path
     from osc_amd.synth import SEED_BASE, generate
-    ref_yaml = os.path.join("/root/reference/config", robot, f"{robot}_config.yaml")
-    yaml_path = ref_yaml if os.path.exists(ref_yaml) else config_path(robot)
-    weights = lit.weights_config(yaml_path)
+    ref_yaml = os.path.join(os.path.dirname(__file__), "golden", "reference_config", robot,
+                            f"{robot}_config.yaml")
+    weights = lit.weights_config(ref_yaml)
     model = load_model(robot)
     d = generate(robot, 2, SEED_BASE + 61, "tumbling", "bernoulli")
     for e in range(2):
