@@ -494,6 +494,13 @@ __device__ __forceinline__ void wave_sync() {
   asm volatile("" ::: "memory");
 }
 
+// A value every lane must hold in a VGPR from here on (emits no instruction).  The optimiser
+// turns a select whose arms are a few f64 operations into an exec-masked branch and sinks the
+// arms into it: the right trade when other wavefronts fill the scalar instructions' slots, the
+// wrong one for the lone wavefront of the one-wave interior point, where every s_and_saveexec /
+// s_cbranch / s_or costs a full issue slot and splits the block the LDS waits hide in.
+__device__ __forceinline__ void in_vgpr(double& x) { asm("" : "+v"(x)); }
+
 // 1/d with one Newton step (v_rcp_f64 is good to ~2^-26; one step gives ~2^-52 in exact
 // arithmetic, a few ulp in practice) -- enough for pivots and barrier terms.
 __device__ __forceinline__ double recip1(double d) {

@@ -533,9 +533,12 @@ __device__ __forceinline__ void ipm_block(
       const int r = l + kRow * t;
       const int rt = (r - 2 * NU) % 6;
       const double sx = (rt & 1) ? -1.0 : 1.0, sy = (rt >= 2) ? -1.0 : 1.0;
-      const double pyr = sx * f0[t] + sy * f1[t] - mu_f * f2[t];
-      const double crow = (rt < 4) ? pyr : ((rt == 4) ? -f2[t] : f2[t]);
-      const double trow = (r & 1) ? -uq[t] : uq[t];
+      double pyr = sx * f0[t] + sy * f1[t] - mu_f * f2[t];
+      in_vgpr(pyr);   // (computed on every lane, not behind a branch on the row's kind)
+      double crow = (rt < 4) ? pyr : ((rt == 4) ? -f2[t] : f2[t]);
+      in_vgpr(crow);
+      double trow = (r & 1) ? -uq[t] : uq[t];
+      in_vgpr(trow);   // (or its read sinks behind a branch on act[t], and is waited for alone)
       out[t] = !act[t] ? 0.0 : ((r < 2 * NU) ? trow : crow);
     }
   };
@@ -571,6 +574,20 @@ __device__ __forceinline__ void ipm_block(
     const double2 a = *reinterpret_cast<const double2*>(wk);
     const double2 b = *reinterpret_cast<const double2*>(wk + 2);
     const double2 c = *reinterpret_cast<const double2*>(wk + 4);
+    if constexpr (SMALL) {
+      // one chain for the three components, its signs picked per lane: the same operations in
+      // the same order as v0 / v1 / v2 below (x - y is x + (-y), bit for bit), less than half of
+      // them issued, and no branch on the lane's component
+      const double t1 = (jc == 0) ? -a.y : a.y;
+      const double t2 = (jc == 1) ? -b.x : b.x;
+      const double t3 = (jc == 2) ? b.y : -b.y;
+      double q = ((a.x + t1) + t2) + t3;
+      double fz = fma(-mu_f, q, -c.x) + c.y;
+      in_vgpr(q);
+      in_vgpr(fz);
+      const double v = (jc == 2) ? fz : q;
+      return jk >= 0 ? v : 0.0;
+    }
     const double v0 = a.x - a.y + b.x - b.y;
     const double v1 = a.x + a.y - b.x - b.y;
     const double v2 = -mu_f * (a.x + a.y + b.x + b.y) - c.x + c.y;
@@ -915,6 +932,11 @@ __device__ __forceinline__ void ipm_block(
   };
   // interior-point stop (the warm fix-up pass is a rescue: its cold solve runs to mu <= 1e-12)
   const double eps_run = (kFix && fixup) ? fmin(P->eps_mu, 1e-12) : P->eps_mu;
+  // read once, ahead of the loop: its wave_sync()s are memory barriers to the compiler, so a
+  // P->field in the loop body is a scalar load and an s_waitcnt lgkmcnt(0) in every iteration --
+  // a cache round trip with nothing to hide it, and a wait for every LDS read in flight as well
+  const int max_iter = P->max_iter, restart_iter = P->restart_iter;
+  const int warm_restart = WARM ? P->warm_restart : 0;
   if constexpr (REFINE) {
     // the interior point's result for this env (osc_ipm_kernel, W_SOL): y, and the active rows
     // as lambda > s with lambda = q > 0
@@ -997,12 +1019,12 @@ __device__ __forceinline__ void ipm_block(
     // the fresh-batch sweeps is still that far off at iteration 20 (tools/ipm_model.py
     // "recenter20": identical iteration counts).
     bool restart = false;
-    if (it == P->restart_iter || (WARM && any_warm && it == P->warm_restart)) {
+    if (it == restart_iter || (WARM && any_warm && it == warm_restart)) {
       double cr = 0.0;
 #pragma unroll
       for (int t = 0; t < NRL; ++t) cr += act[t] ? s[t] * lam[t] : 0.0;
       const bool far = row_sum(cr) / fmax(m_act, 1.0) > 1e-6;
-      const bool mine = far && !done && it == (warm ? P->warm_restart : P->restart_iter);
+      const bool mine = far && !done && it == (warm ? warm_restart : restart_iter);
       restart = __ballot(mine) != 0;
       if (restart) wave_sync();
       if (mine) {
@@ -1017,7 +1039,17 @@ __device__ __forceinline__ void ipm_block(
     if (!init) {
       double cs = 0.0;
 #pragma unroll
-      for (int t = 0; t < NRL; ++t) cs += act[t] ? s[t] * lam[t] : 0.0;
+      for (int t = 0; t < NRL; ++t) {
+        // (inactive rows hold s = 1, lambda = +0 exactly: their product is the select's +0)
+        // (the product rounded on its own, as the select's arm was: no fused multiply-add)
+        if constexpr (SMALL) {
+          double sl = s[t] * lam[t];
+          in_vgpr(sl);
+          cs += sl;
+        } else {
+          cs += act[t] ? s[t] * lam[t] : 0.0;
+        }
+      }
       mu = row_sum(cs) / fmax(m_act, 1.0);
       const bool fresh = it == 0 || mu <= 1e-6 || restart;
       rd_fresh = fresh || !rd_have;
@@ -1029,7 +1061,12 @@ __device__ __forceinline__ void ipm_block(
           rp[t] = fresh ? r : rp[t];
         }
       }
-      if (!done && mu <= eps_run && (!D::WH || rwmax <= P->wheel_tol)) {
+      if constexpr (SMALL) {   // (selects: a lone wave pays a slot per exec-mask instruction)
+        const bool stop = !done && mu <= eps_run && (!D::WH || rwmax <= P->wheel_tol);
+        done = done || stop;
+        st = stop ? OSC_SOLVE_OK : st;
+        it_done = stop ? it : it_done;
+      } else if (!done && mu <= eps_run && (!D::WH || rwmax <= P->wheel_tol)) {
         done = true;
         st = OSC_SOLVE_OK;
         it_done = it;
@@ -1059,7 +1096,7 @@ __device__ __forceinline__ void ipm_block(
           }
         }
       }
-      if (__ballot(!done) == 0 || it >= P->max_iter) {
+      if (__ballot(!done) == 0 || it >= max_iter) {
         if (!done) it_done = it;
         break;
       }
@@ -1068,8 +1105,15 @@ __device__ __forceinline__ void ipm_block(
 #pragma unroll
     for (int t = 0; t < NRL; ++t) {
       const int r = l + kRow * t;
-      inv_s[t] = act[t] ? (init ? 1.0 : recip(s[t])) : 0.0;
-      sVr[r] = init ? 0.0 : (act[t] ? lam[t] : 0.0);
+      if constexpr (SMALL) {
+        // no select on `init`: the start has s = 1 and lambda = 0 on every row, recip(1) is 1
+        // exactly (v_rcp_f64(1) = 1, both Newton corrections 0) and inactive rows hold lambda = +0
+        inv_s[t] = act[t] ? recip(s[t]) : 0.0;
+        sVr[r] = lam[t];
+      } else {
+        inv_s[t] = act[t] ? (init ? 1.0 : recip(s[t])) : 0.0;
+        sVr[r] = init ? 0.0 : (act[t] ? lam[t] : 0.0);
+      }
       sDr[r] = init ? (init_ls(t) ? 1.0 : 0.0) : lam[t] * inv_s[t];
     }
     wave_sync();
