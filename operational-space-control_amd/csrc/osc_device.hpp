@@ -5,7 +5,12 @@
 // sizes).  Included by every kernel translation unit (DESIGN.md §5 lists the units):
 //   osc_setup.hip       kernel 1  osc_setup_kernel       (reduced QP per env)
 //   osc_ipm_*.hip       kernel 2  osc_ipm_kernel & co.   (interior point + refinement), one unit
-//                                                         per robot model
+//                                                         per robot model; osc_ipm.hpp and its
+//                                                         parts: osc_ipm_ldl.hpp (DPP LDL^T and
+//                                                         solves), osc_ipm_lds.hpp (LDS layout),
+//                                                         osc_ipm_rows.hpp (inequality rows),
+//                                                         osc_ipm_wheel.hpp (wheel rotations),
+//                                                         osc_ipm_launch.hpp (kernels, launch_ipm)
 //   osc_dual.hip        kernel 3  osc_dual_kernel        (dual solution, optional)
 //   osc_gi.hip          kernel 4  osc_gi_kernel          (wheel-row active-set fallback)
 //   osc_multi.hip       the two-model grids of osc_batch_solve_multi

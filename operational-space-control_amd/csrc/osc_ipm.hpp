@@ -4,306 +4,18 @@
 // wavefront, and launch_ipm, the pass sequence of one call.  Device code +
 // the launcher template; instantiated once per robot model (osc_ipm_go2.hip, osc_ipm_walter.hip,
 // osc_ipm_wheels.hip) so the three compile in parallel.
+// This file holds ipm_block, the body of one wavefront; its parts are headers of their own:
+// osc_ipm_ldl.hpp (the DPP LDL^T and solves), osc_ipm_lds.hpp (LDS layout per variant),
+// osc_ipm_rows.hpp (products with the inequality rows), osc_ipm_wheel.hpp (wheel-row rotations)
+// and, included last, osc_ipm_launch.hpp (the __global__ wrappers and launch_ipm).
 #pragma once
 #include "osc_internal.hpp"
-#include "osc_ipm_asm.hpp"
+#include "osc_ipm_ldl.hpp"
+#include "osc_ipm_lds.hpp"
+#include "osc_ipm_rows.hpp"
+#include "osc_ipm_wheel.hpp"
 
 namespace osc {
-
-// ============================ kernel 2: interior point, 4 env / wave ========================
-
-// a += bcast_K(src) * ma;  b += bcast_K(src) * mb  (one broadcast source, two slots).
-// NOP = true guards a source that a VALU instruction may have written just before.
-template <int K, bool NOP>
-__device__ __forceinline__ void fmac_bcast2(double& a, double& b, double src, double ma, double mb) {
-  if constexpr (NOP)
-    asm volatile("s_nop 1\n\t"
-                 "v_fmac_f64_dpp %0, %2, %3 row_newbcast:%5 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %1, %2, %4 row_newbcast:%5 row_mask:0xf bank_mask:0xf"
-                 : "+v"(a), "+v"(b) : "v"(src), "v"(ma), "v"(mb), "n"(K));
-  else
-    asm volatile("v_fmac_f64_dpp %0, %2, %3 row_newbcast:%5 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %1, %2, %4 row_newbcast:%5 row_mask:0xf bank_mask:0xf"
-                 : "+v"(a), "+v"(b) : "v"(src), "v"(ma), "v"(mb), "n"(K));
-}
-
-template <int N>
-__device__ __forceinline__ void dot_rows(double& a, double& b, double x0, double x1,
-                                         const double (&ma)[N], const double (&mb)[N]) {
-  double a2 = 0.0, b2 = 0.0;                // two chains: no back-to-back dependent f64 ops
-  if constexpr (N == 24 || N == 32) {       // one asm statement (osc_ipm_asm.hpp): no s_nop per pair
-    dot_rows_asm<N>(a, b, a2, b2, x0, x1, ma, mb);
-    a += a2;
-    b += b2;
-    return;
-  }
-  static_for<0, N>([&](auto ic) {
-    constexpr int i = decltype(ic)::value;
-    if constexpr (i % 2 == 0)
-      fmac_bcast2<i % kRow, i % kRow == 0>(a, b, i < kRow ? x0 : x1, ma[i], mb[i]);
-    else
-      fmac_bcast2<i % kRow, false>(a2, b2, i < kRow ? x0 : x1, ma[i], mb[i]);
-  });
-  a += a2;
-  b += b2;
-}
-
-// LDL^T of an N x N symmetric matrix held one column per lane in two slots: lane l of a row
-// holds column l in c0 and column l+16 in c1.  Right-looking; at step k every lane j > k
-// applies  c_j[i] -= L[i][k] L[j][k] D_k  for i > k with the pivot column entry c_k[i]
-// broadcast by DPP straight into the FMA.  On exit (for slot column j):
-//   c[i], i > j : -L[i][j] D[j] / D[i]  (column j of L, unscaled, times -1/D_i: backward solve)
-//   c[i], i < j : -L[j][i]              (row j of L: forward solve)
-//   c[j]        : -1
-//   dinv0, dinv1: 1 / D[j]
-// thr0, thr1: 1e-13 x the original diagonal (Cholesky-infinity test: a pivot not above it
-// becomes 1e128).  sdinv: 2 x 16 doubles of LDS for this row: every lane writes 1/D_k at step k
-// (one ds_write instead of a lane select), each lane reads its own two back at the end.
-// Slot-1 lanes past N (N < 32) hold a copy of column N-1 (the caller loads jj1 = N-1 there);
-// they are left unmasked while column N-1 is still active, so they stay an exact mirror of it --
-// finite, and never a broadcast source.
-// Look-ahead: pivot k+1's test, broadcast, reciprocal and scaling are issued right after step k's
-// first trailing FMA pair (which finalises column k+1's entry), so their dependent chain overlaps
-// the rest of step k's FMAs instead of stalling between the steps (bitwise the same factor;
-// profiles/r04f_ab_ldl_lookahead.jsonl: Go2 4,096 0.1737 -> 0.1721 ms per solve, 65,536 1.782 ->
-// 1.762, WaLTER 4,096 0.2804 -> 0.2758).
-// (Fusing pass 0's forward elimination into the factorisation -- the right-hand side formed
-// first, its step k riding along the factor's -- measured within noise: Go2 4,096 0.1739 vs
-// 0.1718 ms per solve, 65,536 1.760 vs 1.748, WaLTER 4,096 0.2754 vs 0.2768, and not bitwise;
-// profiles/r04k/ab_fwd_fused.jsonl.)
-// ASM: the scheduled one-statement form (osc_ipm_asm.hpp) -- it claims 12 VGPRs of its own, which
-// the one-wave kernels (512 registers with the AGPRs) have to spare and the two-wave ones do not
-// (their spills grow 12 -> 52 bytes per lane), so those keep the per-pivot form.
-// du: the torque rows' diagonal terms of G'DG (lane q's column q < NU, 0 on the other lanes),
-// added to each pivot where it is taken (round 6: the diagonal of K enters the factorisation only
-// as its pivots, so the same K as adding du to c0[l] up front -- which took a lane select per torque
-// column every iteration -- up to the rounding of the pivots' sums)
-// An empty asm that "rewrites" columns I.. of both slots (ldl_rows: orders their last VALU writes)
-template <int I, int N>
-__device__ __forceinline__ void touch_cols(double (&c0)[N], double (&c1)[N]) {
-  asm volatile("" : "+v"(c0[I]), "+v"(c1[I]));
-  if constexpr (I + 1 < N) touch_cols<I + 1, N>(c0, c1);
-}
-template <int N, bool ASM = true>
-__device__ __forceinline__ void ldl_rows(double (&c0)[N], double (&c1)[N], double* sdinv, int l,
-                                         double& dinv0, double& dinv1, double thr0, double thr1,
-                                         double du) {
-  // pivot k's preparation: -> (t0, t1) = -L[lane][k] for the lanes still to be eliminated
-  auto prep = [&](auto kc, double& t0, double& t1) {
-    constexpr int k = decltype(kc)::value;
-    constexpr int s = k / kRow, kl = k % kRow;
-    const double own = (s == 0) ? c0[k] + du : c1[k];
-    const double dk = bcast_guarded<kl>(own > ((s == 0) ? thr0 : thr1) ? own : 1e128);
-    const double inv = recip1(dk);
-    sdinv[k] = inv;
-    c0[k] = -c0[k] * inv;
-    c1[k] = -c1[k] * inv;
-    // (lanes l > k by a compare on the lane index, osc_device.hpp keep_gt; in slot 1 the mirror
-    // lanes past N keep their multipliers too and so stay exact copies of column N - 1)
-    t0 = keep_gt<k>(l, c0[k]);
-    if constexpr (k < kRow) t1 = c1[k];
-    else t1 = keep_gt<k - kRow>(l, c1[k]);
-  };
-  // one trailing FMA pair of step k, row i (NOP: the DPP source was written just before)
-  auto upd = [&](auto kc, auto ic, double t0, double t1) {
-    constexpr int k = decltype(kc)::value, i = decltype(ic)::value;
-    constexpr int s = k / kRow, kl = k % kRow;
-    constexpr bool nop = (i == k + 1) && (k >= 1) && (i == N - 1);
-    if constexpr (s == 0) {
-      fmac_bcast<kl, nop>(c1[i], c0[i], t1);
-      if constexpr (k < kRow - 1) fmac_bcast_self<kl>(c0[i], t0);
-    } else {
-      fmac_bcast_self<kl, nop>(c1[i], t1);
-    }
-  };
-  if constexpr (ASM && (N == 24 || N == 32)) {
-    // one scheduled asm statement (tools/gen_ipm_asm.py -> osc_ipm_asm.hpp): the same
-    // instructions on the same values, pivot k+1's preparation interleaved with pivot k's FMAs
-    // so that the FMAs are the wait states (no s_nop, no asm-boundary padding)
-    const unsigned addr = static_cast<unsigned>(
-        reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) double*)sdinv));
-    ldl_asm<N>(c0, c1, thr0, thr1, l, addr, du);
-    wave_sync();
-    dinv0 = sdinv[l];
-    dinv1 = sdinv[(l + kRow < N) ? l + kRow : N - 1];
-    return;
-  }
-  // Step 0's DPP reads take columns the caller's C++ just wrote (K = Hr + G'DG): every column goes
-  // through an empty asm first and then one s_nop 1, so no schedule can put a column's VALU write
-  // within the DPP read's two wait states (tests/test_asm_hazards.py; LLVM's ILP scheduler did).
-  touch_cols<0, N>(c0, c1);
-  asm volatile("s_nop 1");
-  double ta0, ta1;
-  prep(std::integral_constant<int, 0>{}, ta0, ta1);
-  static_for<0, N>([&](auto kc) {
-    constexpr int k = decltype(kc)::value;
-    double tb0 = 0.0, tb1 = 0.0;
-    if constexpr (k + 1 < N) {
-      upd(kc, std::integral_constant<int, k + 1>{}, ta0, ta1);
-      prep(std::integral_constant<int, k + 1>{}, tb0, tb1);
-    }
-    static_for<k + 2, N>([&](auto ic) { upd(kc, ic, ta0, ta1); });
-    ta0 = tb0;
-    ta1 = tb1;
-  });
-  wave_sync();
-  dinv0 = sdinv[l];
-  dinv1 = sdinv[(l + kRow < N) ? l + kRow : N - 1];
-}
-
-// Solve K x = r with the factor above; r0 (var l), r1 (var l+16) in, x out.  Every lane of
-// the row is updated at every step (no lane masks): a lane whose value is already final saves
-// it at its own pivot step and may take garbage afterwards.  The factor's row k is pre-scaled
-// by -1/D_k (ldl_rows), so each step is the pivot's broadcast straight into the FMAs -- no
-// multiply in the dependency chain (Go2 4,096: 0.183 -> 0.178 ms per solve;
-// profiles/r03_ab_ldl_prescale.txt):
-//   forward   z = L^-1 r             a_j += a_k * (-L[j][k])
-//   backward  in D-scaled form       a_j += a_k * (-L[k][j] D_j / D_k),  x_j = a_j / D_j
-// The other slot's FMA goes first: the own slot's FMA rewrites the pivot lane (c[k] = -1 there).
-// (Masking each FMA to the lanes it may change through EXEC instead of saving was measured
-// slower: 0.186 ms -- the EXEC writes cost more than the two v_cndmask they replace.)
-// (ldl_fwd_rows / ldl_bwd_rows: the two halves, for callers that act on z in between.)
-template <int N>
-__device__ __forceinline__ void ldl_fwd_rows(const double (&c0)[N], const double (&c1)[N],
-                                             double dinv0, double dinv1,
-                                             double& a0, double& a1, int l) {
-  double z0 = 0.0, z1 = 0.0;                // z_j, saved at step j
-  if constexpr (N == 24 || N == 32) {       // one asm statement (osc_ipm_asm.hpp), bitwise the same
-    ldl_fwd_asm<N>(c0, c1, a0, a1, z0, z1, l);
-    a0 = z0;
-    a1 = z1;
-    return;
-  }
-  static_for<0, N>([&](auto kc) {
-    constexpr int k = decltype(kc)::value;
-    constexpr int s = k / kRow, kl = k % kRow;
-    if constexpr (s == 0) {
-      z0 = sel_eq<kl>(l, a0, z0);   // (its three VALU instructions: the DPP read's wait states)
-      const double p = a0;
-      fmac_bcast<kl>(a1, p, c1[k]);
-      if constexpr (k < kRow - 1) fmac_bcast<kl>(a0, p, c0[k]);
-    } else {
-      z1 = sel_eq<kl>(l, a1, z1);
-      const double p = a1;
-      fmac_bcast<kl>(a1, p, c1[k]);
-    }
-  });
-  a0 = z0;
-  a1 = z1;
-}
-template <int N>
-__device__ __forceinline__ void ldl_bwd_rows(const double (&c0)[N], const double (&c1)[N],
-                                             double dinv0, double dinv1,
-                                             double& a0, double& a1, int l) {
-  double x0 = 0.0, x1 = 0.0;                // D-scaled x_j, saved at step j
-  if constexpr (N == 24 || N == 32) {
-    ldl_bwd_asm<N>(c0, c1, a0, a1, x0, x1, l);
-    a0 = x0 * dinv0;
-    a1 = x1 * dinv1;
-    return;
-  }
-  static_for<0, N>([&](auto kc) {
-    constexpr int k = N - 1 - decltype(kc)::value;
-    constexpr int s = k / kRow, kl = k % kRow;
-    if constexpr (s == 0) {
-      x0 = sel_eq<kl>(l, a0, x0);
-      const double p = a0;
-      if constexpr (k >= 1) fmac_bcast<kl>(a0, p, c0[k]);
-    } else {
-      x1 = sel_eq<kl>(l, a1, x1);
-      const double p = a1;
-      fmac_bcast<kl>(a0, p, c0[k]);
-      if constexpr (k > kRow) fmac_bcast<kl>(a1, p, c1[k]);
-    }
-  });
-  a0 = x0 * dinv0;
-  a1 = x1 * dinv1;
-}
-template <int N>
-__device__ __forceinline__ void ldl_solve_rows(const double (&c0)[N], const double (&c1)[N],
-                                               double dinv0, double dinv1,
-                                               double& a0, double& a1, int l) {
-  ldl_fwd_rows<N>(c0, c1, dinv0, dinv1, a0, a1, l);
-  ldl_bwd_rows<N>(c0, c1, dinv0, dinv1, a0, a1, l);
-}
-
-// WARM = false compiles none of the warm-start / fix-up logic (the cold solve's register budget
-// is unchanged by it: the two-wave Go2 variant would otherwise spill more).
-// LDS doubles of one IPM wavefront.  The one-wave variant must run ONE wavefront per SIMD: when
-// its registers would allow two, the LDS request (> 160 KB / 5 per workgroup) is what keeps the
-// dispatcher from stacking a fifth and sixth workgroup on some CUs while others idle (Go2 in
-// torque coordinates: 26 KB of LDS, 255 VGPRs -> IPM 144 -> 158 us at 4,096 envs until padded).
-// The refinement pass (REFINE) streams Hr from L2 and keeps instead each env's [X | H_dv | f_dv]
-// block of the workspace in LDS (RefineLds).
-template <class D>
-struct RefineLds {
-  static constexpr int X = 0;
-  static constexpr int HD = D::NV * D::NY1P;
-  static constexpr int GD = HD + D::NV * D::NV;
-  static constexpr int SIZE = GD + even(D::NV);   // = W_SOL - W_X in the workspace
-};
-// Refinement modes of the IPM body: none (the interior point alone, handing its result to
-// osc_refine_kernel through W_SOL: warm-started solves past one wave per SIMD, whose fused kernel
-// spills, and models created with osc_model_tuning.refine_steps = 0), the refinement pass alone
-// (osc_refine_kernel), or both in one wavefront (every cold solve and the one-wave warm solve:
-// no hand-off, no second launch).
-constexpr int kRfNone = 0, kRfOnly = 1, kRfFused = 2;
-// Full-space refinement without wheel rows: rounds of active-set changes, and
-// steps per round at most (each env stops at its own convergence, at least refine_steps)
-// (kRefineRounds, kRefineMaxSteps: osc_device.hpp -- the host clamps refine_steps to the latter)
-template <class D, bool SMALL, int RF>
-constexpr bool ipm_hrl() {   // Hr kept in LDS across the interior point's iterations
-  return SMALL && RF != kRfOnly && hr_fits_lds<D>();
-}
-// Two-wave variant (round 6): Hr's first column slot -- columns 0..15, every row
-// (NY x 16 doubles per env) -- is staged into LDS once per solve, and only the second slot's
-// columns are read from the workspace each iteration, as ROWS 16..NY-1 of Hr (Hr is stored exactly
-// symmetric, so row j = column j bitwise): per-lane contiguous 16-byte loads over a contiguous
-// (NY - 16) x NY block.  At 8,192 Go2 envs every Hr re-read used to miss L2 (37.7 MB of Hr against
-// 8 x 4 MB of L2: 7x the algorithmic bytes); the streamed part is now 1.5 KB per env (12 MB).
-// LDS: 246 + 384 doubles per env, 20.2 KB per wave -- eight waves per CU in 160 KB.
-template <class D, bool SMALL, int RF>
-constexpr bool ipm_hrh() {
-  return !SMALL && !D::WH && RF != kRfOnly && D::NY > kRow &&
-         (IpmLayout<D, false>::IL + D::NY * kRow) * 8 * kEnvPerWave * 8 <= 160 * 1024;
-}
-template <class D, bool SMALL, int RF>
-constexpr int hrh_lds_extra() { return ipm_hrh<D, SMALL, RF>() ? D::NY * kRow : 0; }
-// LDS doubles per env beyond the interior point's layout: the refinement's [X | H_dv | f_dv]
-// block, except that a fused pass with Hr in LDS moves X into Hr's region once the first K_A is
-// assembled (registers hold it from then on) and only keeps [H_dv | f_dv] apart.
-// WH: the wheel rows' LDS block of an env: the rotation T (T[i][k] at i * TST + k; odd stride:
-// lanes reading a row of T or a column hit distinct banks), the Q row each column of T carries
-// (-1: free), q1 per Q row, a staging vector for the rotations, and the rows' multipliers.
-template <class D>
-struct WheelLds {
-  static constexpr int NW = D::NW, NY = D::NY, TST = NY + 1;
-  static constexpr int T = 0;
-  static constexpr int PIN = even(NY * TST);
-  static constexpr int Q1 = PIN + even(NY);
-  static constexpr int ROT = Q1 + even(NW);
-  static constexpr int NUV = ROT + even(NY);
-  static constexpr int SIZE = NUV + even(NW);
-};
-template <class D, bool SMALL, int RF>
-constexpr int refine_lds_extra() {
-  if constexpr (D::WH && RF == kRfFused) return WheelLds<D>::SIZE;   // (reads [X | ..] from L2)
-  else if constexpr (RF == kRfNone) return 0;
-  else if constexpr (RF == kRfFused && !SMALL) return 0;   // reads [X | H_dv | f_dv] from L2
-  else if constexpr (RF == kRfFused && ipm_hrl<D, SMALL, RF>())   // (DMA: whole 1 KB rows)
-    return (((RefineLds<D>::SIZE - RefineLds<D>::HD) / 2 + kWave - 1) / kWave) * kWave * 2;
-  else return RefineLds<D>::SIZE;
-}
-// Two-wave variant, measured and not adopted: capping the waves resident per CU so
-// each XCD's Hr working set fits its L2 (slower: the eighth wave per CU hides issue latency), and
-// Hr's upper triangle packed in LDS (2.5 % slower: at full occupancy the Hr loads' latency is
-// already hidden, and the packed addressing costs issue slots).
-template <class D, bool SMALL, int RF = kRfNone>
-constexpr int ipm_lds_doubles() {
-  constexpr int il = IpmLayout<D, ipm_hrl<D, SMALL, RF>()>::IL + refine_lds_extra<D, SMALL, RF>() +
-                     hrh_lds_extra<D, SMALL, RF>();
-  return SMALL ? cmax(kEnvPerWave * il, 160 * 1024 / 5 / 8 + 2) : kEnvPerWave * il;
-}
 
 // The body of one IPM wavefront (envs 4 blk .. 4 blk + 3); `sm` is its ipm_lds_doubles<D, SMALL>
 // doubles of LDS.  Wrapped by osc_ipm_kernel (one model) and osc_ipm_pair_kernel (two models).
@@ -367,11 +79,7 @@ __device__ __forceinline__ void ipm_block(
   constexpr bool kRefG = RF == kRfFused && (!SMALL || D::WH);
   constexpr bool WHR = D::WH && RF == kRfFused;   // the wheel rows' rotated Newton systems
   using WL = WheelLds<D>;
-  double* sWT = B + LY::IL + WL::T;
-  double* sWPin = B + LY::IL + WL::PIN;
-  double* sWQ1 = B + LY::IL + WL::Q1;
-  double* sWRot = B + LY::IL + WL::ROT;
-  double* sWNu = B + LY::IL + WL::NUV;
+  WheelRot W = wheel_rot<D>(B + LY::IL);   // (osc_ipm_wheel.hpp; dead without wheel rows)
   // Hr columns are addressed as wave-uniform base (SGPR pair) + 32-bit lane offset + immediate:
   // 64-bit per-lane address registers for 48 loads do not fit, and their spill reloads
   // (scratch loads share vmcnt) used to serialise the whole prefetch.
@@ -412,11 +120,11 @@ __device__ __forceinline__ void ipm_block(
     if constexpr (WHR) {   // T, the pin map, q1
       const double* we = ws + static_cast<size_t>(env) * D::WS;
 #pragma unroll 8
-      for (int p = l; p < NY * NY; p += kRow) sWT[(p / NY) * WL::TST + p % NY] = we[D::W_T + p];
-      for (int p = l; p < NY; p += kRow) sWPin[p] = we[D::W_PIN + p];
+      for (int p = l; p < NY * NY; p += kRow) W.T[(p / NY) * WL::TST + p % NY] = we[D::W_T + p];
+      for (int p = l; p < NY; p += kRow) W.Pin[p] = we[D::W_PIN + p];
       if (l < D::NW) {
-        sWQ1[l] = we[D::W_AW + l * NY1P + NY];
-        sWNu[l] = 0.0;
+        W.Q1[l] = we[D::W_AW + l * NY1P + NY];
+        W.Nu[l] = 0.0;
       }
     }
     bs.store(B, l);
@@ -508,264 +216,31 @@ __device__ __forceinline__ void ipm_block(
   // fz <= big_number, which would drag fz to ~big_number/2 together with fz >= 0 and start
   // the torque rows far outside their box (tools/ipm_model.py "y0_nofz": Go2 lockstep
   // iterations 14.9 -> 12.6, worst case 22 -> 18).
+  // (the set-up loop above and this lambda stay in the body, not in osc_ipm_rows.hpp: as
+  // functions they cost the two-wave WaLTER kernels scratch)
   auto init_ls = [&](int t) -> bool {
     const int r = l + kRow * t;
     return act[t] && !(r >= 2 * NU && (r - 2 * NU) % 6 == 5);
   };
   STAMP_END(0);
 
-  // (G v)_r for all row slots at once, branch-free, every read issued first (one-wave variant):
-  // torque rows read y_q, contact rows read their contact's three force entries.
-  auto Gv_all = [&](const double* v, double (&out)[NRL]) {
-    double uq[NRL], f0[NRL], f1[NRL], f2[NRL];
-#pragma unroll
-    for (int t = 0; t < NRL; ++t) {
-      const int r = l + kRow * t;
-      const int q = (r < 2 * NU) ? (r >> 1) : 0;
-      const int k = (r >= 2 * NU && r < MI) ? (r - 2 * NU) / 6 : 0;
-      uq[t] = v[q];
-      f0[t] = v[NU + 3 * k];
-      f1[t] = v[NU + 3 * k + 1];
-      f2[t] = v[NU + 3 * k + 2];
-    }
-#pragma unroll
-    for (int t = 0; t < NRL; ++t) {
-      const int r = l + kRow * t;
-      const int rt = (r - 2 * NU) % 6;
-      const double sx = (rt & 1) ? -1.0 : 1.0, sy = (rt >= 2) ? -1.0 : 1.0;
-      double pyr = sx * f0[t] + sy * f1[t] - mu_f * f2[t];
-      in_vgpr(pyr);   // (computed on every lane, not behind a branch on the row's kind)
-      double crow = (rt < 4) ? pyr : ((rt == 4) ? -f2[t] : f2[t]);
-      in_vgpr(crow);
-      double trow = (r & 1) ? -uq[t] : uq[t];
-      in_vgpr(trow);   // (or its read sinks behind a branch on act[t], and is waited for alone)
-      out[t] = !act[t] ? 0.0 : ((r < 2 * NU) ? trow : crow);
-    }
-  };
-  // (G v)_r for row slot t
-  auto Gv = [&](const double* v, int t) -> double {
-    if (!act[t]) return 0.0;
-    const int r = l + kRow * t;
-    if (r < 2 * NU) {
-      const double uq = v[r >> 1];
-      return (r & 1) ? -uq : uq;
-    }
-    const int k = (r - 2 * NU) / 6, rt = (r - 2 * NU) % 6;
-    const int z0 = NU + 3 * k;
-    if (rt < 4) {
-      const double sx = (rt & 1) ? -1.0 : 1.0, sy = (rt >= 2) ? -1.0 : 1.0;
-      return sx * v[z0] + sy * v[z0 + 1] - mu_f * v[z0 + 2];
-    }
-    return (rt == 4) ? -v[z0 + 2] : v[z0 + 2];
-  };
   // variable slots of this lane: j = l + 16 s
   const int j0 = l, j1 = l + kRow;
   const bool v1 = j1 < NY;
   const int jj1 = v1 ? j1 : NY - 1;
   const int jk0 = (j0 >= NU) ? (j0 - NU) / 3 : -1, jc0 = (j0 >= NU) ? (j0 - NU) % 3 : 0;
   const int jk1 = (v1 && j1 >= NU) ? (j1 - NU) / 3 : -1, jc1 = (j1 >= NU) ? (j1 - NU) % 3 : 0;
-  // (G' w)_j for row-space w staged in LDS (inactive rows hold 0)
-  // (G' w)_j for both variable slots of this lane, w row-space in LDS (inactive rows hold 0).
-  // All reads are issued before the arithmetic (one wait, not one per torque row); the contact
-  // part is branch-free: each lane reads its contact's six rows (16-byte pairs) and keeps the
-  // combination of its component jc.
-  auto contact_term = [&](const double* w, int jk, int jc) -> double {
-    const double* wk = w + 2 * NU + 6 * (jk >= 0 ? jk : 0);
-    const double2 a = *reinterpret_cast<const double2*>(wk);
-    const double2 b = *reinterpret_cast<const double2*>(wk + 2);
-    const double2 c = *reinterpret_cast<const double2*>(wk + 4);
-    if constexpr (SMALL) {
-      // one chain for the three components, its signs picked per lane: the same operations in
-      // the same order as v0 / v1 / v2 below (x - y is x + (-y), bit for bit), less than half of
-      // them issued, and no branch on the lane's component
-      const double t1 = (jc == 0) ? -a.y : a.y;
-      const double t2 = (jc == 1) ? -b.x : b.x;
-      const double t3 = (jc == 2) ? b.y : -b.y;
-      double q = ((a.x + t1) + t2) + t3;
-      double fz = fma(-mu_f, q, -c.x) + c.y;
-      in_vgpr(q);
-      in_vgpr(fz);
-      const double v = (jc == 2) ? fz : q;
-      return jk >= 0 ? v : 0.0;
-    }
-    const double v0 = a.x - a.y + b.x - b.y;
-    const double v1 = a.x + a.y - b.x - b.y;
-    const double v2 = -mu_f * (a.x + a.y + b.x + b.y) - c.x + c.y;
-    const double v = (jc == 0) ? v0 : ((jc == 1) ? v1 : v2);
-    return jk >= 0 ? v : 0.0;
-  };
-  auto GTw2 = [&](const double* w, double& r0, double& r1) {
-    // torque rows +-e_q: lane j0 < NU picks up w[2 j0] - w[2 j0 + 1]; slot j1 >= 16 > NU is a
-    // contact variable
-    const double2 p = *reinterpret_cast<const double2*>(w + 2 * (j0 < NU ? j0 : 0));
-    const double k0 = contact_term(w, jk0, jc0), k1 = contact_term(w, jk1, jc1);
-    r0 = (j0 < NU ? p.x - p.y : 0.0) + k0;
-    r1 = k1;
-  };
-  // contact block column (B[0..2][jc]) of var slot in contact jk, from D = lambda/s
-  auto contact_col = [&](int jk, int jc, double& v0, double& v1_, double& v2) {
-    const double* dk = sDr + 2 * NU + 6 * jk;
-    const double s4 = dk[0] + dk[1] + dk[2] + dk[3];
-    const double sxy = dk[0] - dk[1] - dk[2] + dk[3];
-    const double sx = dk[0] - dk[1] + dk[2] - dk[3];
-    const double sy = dk[0] + dk[1] - dk[2] - dk[3];
-    const double b00 = s4, b11 = s4, b01 = sxy, b02 = -mu_f * sx, b12 = -mu_f * sy,
-                 b22 = mu_f * mu_f * s4 + dk[4] + dk[5];
-    v0 = (jc == 0) ? b00 : (jc == 1) ? b01 : b02;
-    v1_ = (jc == 0) ? b01 : (jc == 1) ? b11 : b12;
-    v2 = (jc == 0) ? b02 : (jc == 1) ? b12 : b22;
-  };
+  const RowLane L{l, j0, j1, jj1, v1, jk0, jc0, jk1, jc1, mu_f};   // (osc_ipm_rows.hpp)
 
-  // Wheel no-slip rows (WH): Q [y; 1] = 0, orthonormal rows (setup_env).  The Newton systems of
-  // the interior point and the refinement are solved in y^ = T'y, T = [rows of Q | null-space
-  // basis] (setup_env): K^ = H^ + sum_r D_r (T'g_r)(T'g_r)' assembled from the rows g_r of G one
-  // original coordinate at a time (no cancellation of large entries), the coordinates along Q's
-  // rows pinned (identity rows, step = -(Q y + q1): the rows hold after every step).  The
-  // iterate itself stays in y coordinates.  (An earlier Schur-complement treatment of the rows on
-  // K's factor lost the Newton steps' accuracy next to nearly dependent active rows: DESIGN.md §3.)
   constexpr int NW = D::NW;
-  // this lane's slots: pinned?  (the Q row's q1 for the residual)
-  bool pin0 = false, pin1 = false;
-  double q10 = 0.0, q11 = 0.0;
-  auto rot_load_pins = [&]() {
-    if constexpr (WHR) {
-      const double p0v = sWPin[j0], p1v = sWPin[jj1];
-      pin0 = p0v != -1.0;
-      pin1 = v1 && p1v != -1.0;
-      q10 = p0v >= 0.0 ? sWQ1[static_cast<int>(p0v)] : 0.0;
-      q11 = (v1 && p1v >= 0.0) ? sWQ1[static_cast<int>(p1v)] : 0.0;
-    }
-  };
-  // T'v and T v for a y-space vector held in the lane slots (staged through sWRot)
-  auto rot_in = [&](double v0, double v1v, double& o0, double& o1) {
-    wave_sync();
-    sWRot[j0] = v0;
-    if (v1) sWRot[j1] = v1v;
-    wave_sync();
-    double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-    for (int i = 0; i < NY; ++i) {
-      const double r = sWRot[i];
-      a0 = fma(sWT[i * WL::TST + j0], r, a0);
-      a1 = fma(sWT[i * WL::TST + jj1], r, a1);
-    }
-    o0 = a0;
-    o1 = a1;
-    wave_sync();
-  };
-  auto rot_out = [&](double v0, double v1v, double& o0, double& o1) {
-    wave_sync();
-    sWRot[j0] = v0;
-    if (v1) sWRot[j1] = v1v;
-    wave_sync();
-    double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-    for (int k = 0; k < NY; ++k) {
-      const double r = sWRot[k];
-      a0 = fma(sWT[j0 * WL::TST + k], r, a0);
-      a1 = fma(sWT[jj1 * WL::TST + k], r, a1);
-    }
-    o0 = a0;
-    o1 = a1;
-    wave_sync();
-  };
   // rq: the rows' residual at the current y, on the pinned slots (q1 at the start, y = 0)
   double rq0 = 0.0, rq1 = 0.0, rwmax = 0.0;
-  rot_load_pins();
-  rq0 = pin0 ? q10 : 0.0;
-  rq1 = pin1 ? q11 : 0.0;
+  if constexpr (WHR) rot_load_pins<D>(W, L);
+  rq0 = W.pin0 ? W.q10 : 0.0;
+  rq1 = W.pin1 ? W.q11 : 0.0;
 
   double c0[NY], c1[NY];
   double dinv0, dinv1;
-  // G'DG's contact blocks into K's columns (c0 / c1), row by row (round 6): the rows of contact k
-  // are NU + 3k .. NU + 3k + 2, and the lanes whose column lies in contact k form a compile-time lane
-  // range of each slot -- so each row takes its entry (a, b or cc by the row's component) masked
-  // to that range, and rows no lane of a slot reaches are not touched.  (It was a select per row
-  // of all 12 contact rows against the lane's runtime contact index, behind a branch per slot.)
-  auto add_contact_blocks = [&](double& dg0, double& dg1) __attribute__((always_inline)) {
-    double a0, b0, e0, a1, b1, e1;
-    contact_col(jk0 >= 0 ? jk0 : 0, jc0, a0, b0, e0);
-    contact_col(jk1 >= 0 ? jk1 : 0, jc1, a1, b1, e1);
-    dg0 += jk0 >= 0 ? ((jc0 == 0) ? a0 : (jc0 == 1) ? b0 : e0) : 0.0;
-    dg1 += jk1 >= 0 ? ((jc1 == 0) ? a1 : (jc1 == 1) ? b1 : e1) : 0.0;
-    static_for<0, NC>([&](auto Kc) __attribute__((always_inline)) {
-      constexpr int k = decltype(Kc)::value, r0 = NU + 3 * k;
-      constexpr unsigned m0 = r0 <= kRow - 1 ? lanes_from(r0, r0 + 2) : 0u;   // slot 0: lane = row
-      constexpr unsigned m1 = lanes_from(r0 - kRow, r0 + 2 - kRow);           // slot 1: row - 16
-      if constexpr (m0 != 0u) {
-        const unsigned long long m = mask_here<rows_mask(m0)>();
-        c0[r0] += keep_m(m, a0);
-        c0[r0 + 1] += keep_m(m, b0);
-        c0[r0 + 2] += keep_m(m, e0);
-      }
-      if constexpr (m1 != 0u) {
-        const unsigned long long m = mask_here<rows_mask(m1)>();
-        c1[r0] += keep_m(m, a1);
-        c1[r0 + 1] += keep_m(m, b1);
-        c1[r0 + 2] += keep_m(m, e1);
-      }
-    });
-  };
-  // WH: c0 / c1 hold H^'s columns j0, jj1; add T'(G'DG)T from sDr (D per row slot) one original
-  // coordinate i at a time -- column j gains coef_i(j) T[i][:], coef_i(j) = (G'DG)[i][:] T[:][j]
-  // (torque rows: diagonal; a contact's rows: its 3 x 3 block) -- then pin Q's coordinates.
-  // Returns the assembled diagonal entries (the pivot threshold's reference).
-  auto assemble_rot = [&](double& dg0r, double& dg1r) __attribute__((always_inline)) {
-    if constexpr (WHR) {
-      // K^ columns j0, jj1 += T' (B T)[:, j] with B = G'DG (diagonal on u, a 3 x 3 block per
-      // contact), one row i of T at a time: a = (B T)[i, j] from the lane's own entries of T, then
-      // c[m] += a T[i][m] with T[i][m] broadcast from the lane that owns column m
-      // (v_fmac_f64_dpp row_newbcast) -- each lane reads its own two entries of row i instead of
-      // the whole row from LDS (the per-iteration product of the wheel rows: NY^3 per env)
-      auto rank1 = [&](double a0, double a1, double t0, double t1) __attribute__((always_inline)) {
-        static_for<0, kRow>([&](auto K) __attribute__((always_inline)) {
-          constexpr int k = decltype(K)::value;
-          if constexpr (k < NY) {
-            fmac_bcast<k, k == 0>(c0[k], t0, a0);
-            fmac_bcast<k>(c1[k], t0, a1);
-          }
-          if constexpr (k + kRow < NY) {
-            fmac_bcast<k, k == 0>(c0[k + kRow], t1, a0);
-            fmac_bcast<k>(c1[k + kRow], t1, a1);
-          }
-        });
-      };
-#pragma unroll
-      for (int i = 0; i < NU; ++i) {
-        const double d = sDr[2 * i] + sDr[2 * i + 1];
-        const double t0 = sWT[i * WL::TST + j0], t1 = sWT[i * WL::TST + jj1];
-        rank1(d * t0, d * t1, t0, t1);
-      }
-      static_for<0, NC>([&](auto Kc) __attribute__((always_inline)) {
-        constexpr int k = decltype(Kc)::value, zb = NU + 3 * k;
-        double t0r[3], t1r[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          t0r[r] = sWT[(zb + r) * WL::TST + j0];
-          t1r[r] = sWT[(zb + r) * WL::TST + jj1];
-        }
-        static_for<0, 3>([&](auto Ci) __attribute__((always_inline)) {
-          constexpr int ci = decltype(Ci)::value;
-          double b0, b1, b2;   // row ci of contact k's block (symmetric: its column ci)
-          contact_col(k, ci, b0, b1, b2);
-          const double a0 = b0 * t0r[0] + b1 * t0r[1] + b2 * t0r[2];
-          const double a1 = b0 * t1r[0] + b1 * t1r[1] + b2 * t1r[2];
-          rank1(a0, a1, t0r[ci], t1r[ci]);
-        });
-      });
-      double d0 = 0.0, d1 = 0.0;
-#pragma unroll
-      for (int m = 0; m < NY; ++m) {
-        const bool pm = sWPin[m] != -1.0;
-        c0[m] = pin0 ? ((m == j0) ? 1.0 : 0.0) : (pm ? 0.0 : c0[m]);
-        c1[m] = pin1 ? ((m == jj1) ? 1.0 : 0.0) : (pm ? 0.0 : c1[m]);
-        d0 = (m == j0) ? c0[m] : d0;
-        d1 = (m == jj1) ? c1[m] : d1;
-      }
-      dg0r = d0;
-      dg1r = d1;
-    }
-  };
   // One-wave variant whose Hr does not fit the LDS (WaLTER: 32 x 32 x 4 envs): the lane's two Hr
   // columns are loaded once and kept in registers across the iterations (the one-wave kernel has
   // 512 of them, AGPRs included) instead of being re-read from L2 every iteration.
@@ -910,26 +385,6 @@ __device__ __forceinline__ void ipm_block(
   };
   bool parked = false;   // park pass: this row's env went to the park area (no outputs here)
   bool refined = false;
-  // WH with the duals requested: the wheel rows' multipliers (W_NU; the refinement's where it is
-  // kept, else the interior point's centre) -- a diagnostic of the workspace since round 4: the
-  // dual kernel recovers every multiplier, the wheel rows' included, from the design vector.
-  // (w = L' nu: the multipliers of the rows [V X | V x0 - vs] before their orthonormalisation,
-  // which the dual kernel maps back to E's rows; every lane of the env's row takes part)
-  auto put_wheel_duals = [&](double nu) {
-    if constexpr (D::WH) {
-      if (want_dual) {
-        const double* Lw = ws + static_cast<size_t>(env) * D::WS + D::W_WL;
-        const int lc = l < NW ? l : 0;
-        double acc = 0.0;
-        static_for<0, NW>([&](auto W) {
-          constexpr int w = decltype(W)::value;
-          acc = fma(Lw[w * NW + lc], bcast_guarded<w>(nu), acc);
-        });
-        if (write_out && l < NW)
-          const_cast<double*>(ws)[static_cast<size_t>(env) * D::WS + D::W_NU + l] = acc;
-      }
-    }
-  };
   // interior-point stop (the warm fix-up pass is a rescue: its cold solve runs to mu <= 1e-12)
   const double eps_run = (kFix && fixup) ? fmin(P->eps_mu, 1e-12) : P->eps_mu;
   // read once, ahead of the loop: its wave_sync()s are memory barriers to the compiler, so a
@@ -979,7 +434,7 @@ __device__ __forceinline__ void ipm_block(
         const double dlt = P->warm_delta;
 #pragma unroll
         for (int t = 0; t < NRL; ++t) {
-          const double gy = Gv(sVy, t);
+          const double gy = Gv<D>(L, act, sVy, t);
           const double wl = wst[D::WW_L + l + kRow * t];
           s[t] = act[t] ? fmax(h[t] - gy, dlt) : 1.0;
           lam[t] = act[t] ? fmax(wl, dlt) : 0.0;
@@ -1005,9 +460,9 @@ __device__ __forceinline__ void ipm_block(
         // the wheel rows' residual at the warm y (this tick's rows: directions and mask are new
         // every tick; the first Newton step's pinned coordinates step onto them exactly)
         double yh0, yh1;
-        rot_in(y0, y1, yh0, yh1);
-        rq0 = pin0 ? yh0 + q10 : 0.0;
-        rq1 = pin1 ? yh1 + q11 : 0.0;
+        rot_in<D>(W, L, y0, y1, yh0, yh1);
+        rq0 = W.pin0 ? yh0 + W.q10 : 0.0;
+        rq1 = W.pin1 ? yh1 + W.q11 : 0.0;
         rwmax = row_max(fmax(fabs(rq0), fabs(rq1)));
       }
     }
@@ -1030,7 +485,7 @@ __device__ __forceinline__ void ipm_block(
       if (mine) {
 #pragma unroll
         for (int t = 0; t < NRL; ++t) {
-          const double slack = h[t] - Gv(sVy, t);
+          const double slack = h[t] - Gv<D>(L, act, sVy, t);
           s[t] = act[t] ? fmax(slack, 0.0) + 1.0 : 1.0;
           lam[t] = act[t] ? 1.0 : 0.0;
         }
@@ -1057,7 +512,7 @@ __device__ __forceinline__ void ipm_block(
         wave_sync();
 #pragma unroll
         for (int t = 0; t < NRL; ++t) {
-          const double r = act[t] ? Gv(sVy, t) + s[t] - h[t] : 0.0;
+          const double r = act[t] ? Gv<D>(L, act, sVy, t) + s[t] - h[t] : 0.0;
           rp[t] = fresh ? r : rp[t];
         }
       }
@@ -1124,14 +579,14 @@ __device__ __forceinline__ void ipm_block(
     double rd0 = rdc0, rd1 = rdc1;
     if (!kRdCarry || init || __ballot(rd_fresh && !done) != 0) {   // (wave-uniform)
       double rn0, rn1;
-      GTw2(sVr, rn0, rn1);
-      if constexpr (WHR) rot_in(rn0, rn1, rn0, rn1);   // T'G'lam
+      GTw2<D, SMALL>(L, sVr, rn0, rn1);
+      if constexpr (WHR) rot_in<D>(W, L, rn0, rn1, rn0, rn1);   // T'G'lam
       rn0 += g0;
       rn1 += g1;
       if constexpr (WHR) {   // rd^ += H^ y^
         if (!init) {
           double yh0, yh1;
-          rot_in(y0, y1, yh0, yh1);
+          rot_in<D>(W, L, y0, y1, yh0, yh1);
           dot_rows<NY>(rn0, rn1, yh0, yh1, c0, c1);
         }
       } else {
@@ -1146,7 +601,7 @@ __device__ __forceinline__ void ipm_block(
     STAMP_BEGIN();
     // G_u' D G_u is diagonal, d_q = D[2q] + D[2q+1] on (q, q): lane q's column j0 = q
     if constexpr (WHR) {
-      assemble_rot(dg0, dg1);
+      assemble_rot<D>(W, L, sDr, c0, c1, dg0, dg1);
     } else {
       static_assert(D::NU <= kRow, "torque variables in the first column slot");
       const double2 dd = *reinterpret_cast<const double2*>(sDr + 2 * (j0 < NU ? j0 : 0));
@@ -1155,7 +610,7 @@ __device__ __forceinline__ void ipm_block(
     }
     STAMP_END(9);
     STAMP_BEGIN();
-    if constexpr (!WHR) add_contact_blocks(dg0, dg1);
+    if constexpr (!WHR) add_contact_blocks<D>(L, sDr, c0, c1, dg0, dg1);
     wave_sync();
     STAMP_END(2);
     STAMP_BEGIN();
@@ -1178,11 +633,11 @@ __device__ __forceinline__ void ipm_block(
         sVr[l + kRow * t] = init ? (init_ls(t) ? h[t] : 0.0) : (rc - lam[t] * rp[t]) * inv_s[t];
       }
       wave_sync();
-      GTw2(sVr, dy0, dy1);
+      GTw2<D, SMALL>(L, sVr, dy0, dy1);
       if constexpr (WHR) {   // in y^: T'(G'w) - rd^, the pinned slots step to the rows
-        rot_in(dy0, dy1, dy0, dy1);
-        dy0 = pin0 ? -rq0 : dy0 - rd0;
-        dy1 = pin1 ? -rq1 : dy1 - rd1;
+        rot_in<D>(W, L, dy0, dy1, dy0, dy1);
+        dy0 = W.pin0 ? -rq0 : dy0 - rd0;
+        dy1 = W.pin1 ? -rq1 : dy1 - rd1;
       } else {
         dy0 -= rd0;
         dy1 -= rd1;
@@ -1190,7 +645,7 @@ __device__ __forceinline__ void ipm_block(
       STAMP_END(4);
       STAMP_BEGIN();
       ldl_solve_rows<NY>(c0, c1, dinv0, dinv1, dy0, dy1, l);
-      if constexpr (WHR) rot_out(dy0, dy1, dy0, dy1);
+      if constexpr (WHR) rot_out<D>(W, L, dy0, dy1, dy0, dy1);
       sVy2[j0] = dy0;
       if (v1) sVy2[j1] = dy1;
       wave_sync();
@@ -1200,11 +655,11 @@ __device__ __forceinline__ void ipm_block(
       // step to the boundary, division-free: 1 / max(1, max_r(-ds/s), max_r(-dl/lambda))
       double rmax = 1.0;
       double gdy_all[NRL];
-      if constexpr (SMALL) Gv_all(sVy2, gdy_all);
+      if constexpr (SMALL) Gv_all<D>(L, act, sVy2, gdy_all);
 #pragma unroll
       for (int t = 0; t < NRL; ++t) {
         const double rc = fma(s[t], lam[t], dsdl[t]) - sig_mu;
-        const double gdy = SMALL ? gdy_all[t] : Gv(sVy2, t);
+        const double gdy = SMALL ? gdy_all[t] : Gv<D>(L, act, sVy2, t);
         ds[t] = act[t] ? -rp[t] - gdy : 0.0;
         dl[t] = -(rc + lam[t] * ds[t]) * inv_s[t];
         const double inv_l = (act[t] && !init) ? recip1(lam[t]) : 0.0;
@@ -1298,9 +753,9 @@ __device__ __forceinline__ void ipm_block(
     wave_sync();
     if constexpr (WHR) {   // the rows' residual at the new iterate (next step, stop test)
       double yh0, yh1;
-      rot_in(y0, y1, yh0, yh1);
-      rq0 = pin0 ? yh0 + q10 : 0.0;
-      rq1 = pin1 ? yh1 + q11 : 0.0;
+      rot_in<D>(W, L, y0, y1, yh0, yh1);
+      rq0 = W.pin0 ? yh0 + W.q10 : 0.0;
+      rq1 = W.pin1 ? yh1 + W.q11 : 0.0;
       rwmax = row_max(fmax(fabs(rq0), fabs(rq1)));
     }
     STAMP_END(7);
@@ -1412,13 +867,13 @@ __device__ __forceinline__ void ipm_block(
         double dg0 = hdg0, dg1 = hdg1, du = 0.0;
         if constexpr (WHR) {
           wave_sync();
-          assemble_rot(dg0, dg1);
+          assemble_rot<D>(W, L, sDr, c0, c1, dg0, dg1);
         } else {
           const double2 dd = *reinterpret_cast<const double2*>(sDr + 2 * (j0 < NU ? j0 : 0));
           du = (j0 < NU) ? dd.x + dd.y : 0.0;
           dg0 += du;
         }
-        if constexpr (!WHR) add_contact_blocks(dg0, dg1);
+        if constexpr (!WHR) add_contact_blocks<D>(L, sDr, c0, c1, dg0, dg1);
         // HRL: X is copied global -> LDS by DMA (no registers) into Hr's region -- free now, K_A
         // is in registers -- issued before the factorisation, waited for after it, so its latency
         // hides behind the LDL^T.  A DMA wave-instruction writes 16 B per lane to a wave-uniform
@@ -1490,9 +945,9 @@ __device__ __forceinline__ void ipm_block(
           const double* yv = sVy;
           if constexpr (WHR) {
             double yh0, yh1;
-            rot_in(ya0, ya1, yh0, yh1);
-            rq0 = pin0 ? yh0 + q10 : 0.0;
-            rq1 = pin1 ? yh1 + q11 : 0.0;
+            rot_in<D>(W, L, ya0, ya1, yh0, yh1);
+            rq0 = W.pin0 ? yh0 + W.q10 : 0.0;
+            rq1 = W.pin1 ? yh1 + W.q11 : 0.0;
             sVy2[j0] = yh0;
             if (v1) sVy2[j1] = yh1;
             wave_sync();
@@ -1565,10 +1020,10 @@ __device__ __forceinline__ void ipm_block(
           double r0 = (j0 < NU ? wu : wz) * ya0, r1 = (jj1 < NU ? wu : wz) * ya1;
           double gm0, gm1;
           if constexpr (WHR) {
-            GTw2(sVr, gm0, gm1);
+            GTw2<D, SMALL>(L, sVr, gm0, gm1);
             r0 += gm0;
             r1 += gm1;
-            rot_in(r0, r1, r0, r1);
+            rot_in<D>(W, L, r0, r1, r0, r1);
           }
 #pragma unroll kUr
           for (int i = 0; i < NV; ++i) {
@@ -1576,36 +1031,36 @@ __device__ __forceinline__ void ipm_block(
             r1 = fma(rX[i * NY1P + jj1], sDr[i], r1);
           }
           if constexpr (!WHR) {   // (this order: the feature-off results stay bitwise)
-            GTw2(sVr, gm0, gm1);
+            GTw2<D, SMALL>(L, sVr, gm0, gm1);
             r0 += gm0;
             r1 += gm1;
           }
           if constexpr (WHR) {
             // the pinned coordinates of r^ are Q (grad f + G_A' mu): their negatives are the rows'
             // multipliers (least squares; the last step's stand)
-            const double p0v = sWPin[j0], p1v = sWPin[jj1];
-            if (p0v >= 0.0) sWNu[static_cast<int>(p0v)] = -r0;
-            if (v1 && p1v >= 0.0) sWNu[static_cast<int>(p1v)] = -r1;
+            const double p0v = W.Pin[j0], p1v = W.Pin[jj1];
+            if (p0v >= 0.0) W.Nu[static_cast<int>(p0v)] = -r0;
+            if (v1 && p1v >= 0.0) W.Nu[static_cast<int>(p1v)] = -r1;
           }
           wave_sync();
           double R3[NRL];
 #pragma unroll
           for (int t = 0; t < NRL; ++t) {
-            R3[t] = (Dr[t] != 0.0) ? Gv(sVy, t) - h[t] : 0.0;
+            R3[t] = (Dr[t] != 0.0) ? Gv<D>(L, act, sVy, t) - h[t] : 0.0;
             sVr[l + kRow * t] = Dr[t] * R3[t];
           }
           wave_sync();
           double b0, b1;
-          GTw2(sVr, b0, b1);
-          if constexpr (WHR) rot_in(b0, b1, b0, b1);
+          GTw2<D, SMALL>(L, sVr, b0, b1);
+          if constexpr (WHR) rot_in<D>(W, L, b0, b1, b0, b1);
           double d0 = -r0 - b0, d1 = -r1 - b1;
           if constexpr (WHR) {
-            d0 = pin0 ? -rq0 : d0;
-            d1 = pin1 ? -rq1 : d1;
+            d0 = W.pin0 ? -rq0 : d0;
+            d1 = W.pin1 ? -rq1 : d1;
           }
           ldl_solve_rows<NY>(c0, c1, dinv0, dinv1, d0, d1, l);
           if constexpr (WHR) {
-            rot_out(d0, d1, d0, d1);
+            rot_out<D>(W, L, d0, d1, d0, d1);
             dlast = row_max(fmax(fabs(d0), v1 ? fabs(d1) : 0.0));
           }
           const bool frz = !kOldWh && conv;   // converged at an earlier step: no further move
@@ -1617,7 +1072,8 @@ __device__ __forceinline__ void ipm_block(
           if (v1) sVy2[j1] = d1;
           wave_sync();
 #pragma unroll
-          for (int t = 0; t < NRL; ++t) mur[t] += frz ? 0.0 : Dr[t] * (Gv(sVy2, t) + R3[t]);
+          for (int t = 0; t < NRL; ++t)
+            mur[t] += frz ? 0.0 : Dr[t] * (Gv<D>(L, act, sVy2, t) + R3[t]);
           ya0 += d0;
           ya1 += d1;
           wave_sync();
@@ -1642,7 +1098,7 @@ __device__ __forceinline__ void ipm_block(
         double nviol = 0.0, vl = 0.0, gv[NRL];
 #pragma unroll
         for (int t = 0; t < NRL; ++t) {
-          gv[t] = Gv(sVy, t) - h[t];
+          gv[t] = Gv<D>(L, act, sVy, t) - h[t];
           vl = fmax(vl, (act[t] && Dr[t] == 0.0 && gv[t] > ytol) ? gv[t] : 0.0);
         }
         const double vbest = WHR ? 0.0 : row_max(vl);
@@ -1692,7 +1148,7 @@ __device__ __forceinline__ void ipm_block(
           yk1 = ya1;
           if constexpr (WHR) {
             dk = dlast;
-            nuk = l < NW ? sWNu[l] : 0.0;
+            nuk = l < NW ? W.Nu[l] : 0.0;
           }
         }
         STAMP_END(11);
@@ -1724,8 +1180,8 @@ __device__ __forceinline__ void ipm_block(
       double wres = 0.0;
       if constexpr (WHR) {
         double yh0, yh1;
-        rot_in(ya0, ya1, yh0, yh1);
-        wres = row_max(fmax(pin0 ? fabs(yh0 + q10) : 0.0, pin1 ? fabs(yh1 + q11) : 0.0));
+        rot_in<D>(W, L, ya0, ya1, yh0, yh1);
+        wres = row_max(fmax(W.pin0 ? fabs(yh0 + W.q10) : 0.0, W.pin1 ? fabs(yh1 + W.q11) : 0.0));
       }
       const bool keep = !viol_env && row_min(ok) == 1.0 && wres <= ytol;
       if (mine && keep) {
@@ -1751,7 +1207,9 @@ __device__ __forceinline__ void ipm_block(
              64 * (wres <= ytol ? 0 : 1) + 128 * (row_min(dlast <= 1e-10 * (1.0 + myr) ? 1.0 : 0.0) == 1.0 ? 0 : 1) +
              256 * (row_min(mv <= 0.1 * (1.0 + myr) ? 1.0 : 0.0) == 1.0 ? 0 : 1);
 #endif
-      put_wheel_duals((mine && keep && l < NW) ? (settled ? nuk : sWNu[l]) : 0.0);
+      if constexpr (D::WH)
+        put_wheel_duals<D>(ws, env, l, want_dual, write_out,
+                           (mine && keep && l < NW) ? (settled ? nuk : W.Nu[l]) : 0.0);
       wave_sync();
       sVy[j0] = y0;
       if (v1) sVy[j1] = y1;
@@ -1762,7 +1220,9 @@ __device__ __forceinline__ void ipm_block(
 #ifdef OSC_STAMPS
   if constexpr (RF == kRfFused) STAMP_STORE();
 #endif
-  if (!refined) put_wheel_duals(0.0);
+  if constexpr (D::WH) {
+    if (!refined) put_wheel_duals<D>(ws, env, l, want_dual, write_out, 0.0);
+  }
   // ---------------- outputs: tau = y_u;  x = (dv, u, z) with dv = X [y; 1] -----------------
   if (REFINE && !refined) {   // the interior point kernel's outputs stand
     if (write_out && l == 0 && gstatus && st == OSC_SOLVE_UNREFINED) gstatus[env] = st;
@@ -1777,7 +1237,7 @@ __device__ __forceinline__ void ipm_block(
     const double* yv = sVy;
     if constexpr (WHR) {   // X^ = X'T: dv = X^ [T'y; 1]
       double yh0, yh1;
-      rot_in(y0, y1, yh0, yh1);
+      rot_in<D>(W, L, y0, y1, yh0, yh1);
       sVy2[j0] = yh0;
       if (v1) sVy2[j1] = yh1;
       wave_sync();
@@ -1828,209 +1288,6 @@ __device__ __forceinline__ void ipm_block(
   }
 }
 
-template <class D, bool SMALL, bool WARM, int RF = kRfNone>
-#ifndef OSC_LARGE_WAVES
-#define OSC_LARGE_WAVES 2
-#endif
-__global__ __launch_bounds__(kWave, SMALL ? 1 : OSC_LARGE_WAVES) void osc_ipm_kernel(
-    const DevParams* __restrict__ P, int nenv, const double* __restrict__ gmask,
-    const double* __restrict__ ws, double* __restrict__ gtau, double* __restrict__ gx,
-    int32_t* __restrict__ gstatus, int32_t* __restrict__ giters, double* __restrict__ gwarm,
-    int flags) {
-  // one-wave variant: four workgroups per CU (160 KB of LDS), never five.  (The opt-in wheel
-  // rows' Schur blocks take it to 53 KB per wave: three per CU)
-  static_assert(!SMALL || ipm_lds_doubles<D, SMALL, RF>() * 8 <= 160 * 1024 / (D::WH ? 3 : 4),
-                "IPM LDS");
-  static_assert(ipm_lds_doubles<D, SMALL, RF>() * 8 <= 64 * 1024, "IPM LDS per workgroup");
-  __shared__ __attribute__((aligned(16))) double sm[ipm_lds_doubles<D, SMALL, RF>()];
-  // flags bit 2 (warm-started, refinement fused): the cold fix-up pass runs in the same launch,
-  // each wavefront right after its own warm pass (its statuses are its own global stores: the
-  // fence makes them visible to its lanes) -- the separate fix-up launch, 1,024 wavefronts that
-  // mostly exit at once, cost 4.2 us of a 139 us Go2 4,096 warm tick
-  ipm_block<D, SMALL, WARM, RF>(P, static_cast<int>(blockIdx.x), nenv, gmask, ws, gtau, gx,
-                                gstatus, giters, gwarm, flags & 3, sm);
-  if constexpr (WARM || RF == kRfFused) {
-    if (flags & 4) {   // (a second inlined body: a loop over both passes spilled 180 B per lane)
-      // the statuses it reads are this wavefront's own stores: a workgroup-scope fence (their
-      // completion) is enough -- a device-scope __threadfence() wrote the L2 back in every
-      // wavefront, +15-18 % at 8,192 / 65,536 envs where two waves share each SIMD
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-      ipm_block<D, SMALL, WARM, RF>(P, static_cast<int>(blockIdx.x), nenv, gmask, ws, gtau, gx,
-                                    gstatus, giters, gwarm, (flags & 2) | 1, sm);
-    }
-  }
-}
-
-// The cold fused solve split in two passes for lockstep compaction (ParkArgs): CP = kCpPark
-// over every env's wavefront, then CP = kCpResume over the parked envs, packed.
-template <class D, bool SMALL, int CP>
-__global__ __launch_bounds__(kWave, SMALL ? 1 : 2) void osc_ipm_compact_kernel(
-    const DevParams* __restrict__ P, int nenv, const double* __restrict__ gmask,
-    const double* __restrict__ ws, double* __restrict__ gtau, double* __restrict__ gx,
-    int32_t* __restrict__ gstatus, int32_t* __restrict__ giters, int flags, ParkArgs PA) {
-  __shared__ __attribute__((aligned(16))) double sm[ipm_lds_doubles<D, SMALL, kRfFused>()];
-  ipm_block<D, SMALL, false, kRfFused, CP>(P, static_cast<int>(blockIdx.x), nenv, gmask, ws, gtau,
-                                           gx, gstatus, giters, nullptr, flags, sm, PA);
-}
-
-// The full-space refinement pass (torque coordinates): the same body with the interior-point
-// loop compiled out, started from the result the interior point left in W_SOL, so its extra
-// state never weighs on the interior point's register allocation.
-template <class D, bool SMALL>
-__global__ __launch_bounds__(kWave, SMALL ? 1 : 2) void osc_refine_kernel(
-    const DevParams* __restrict__ P, int nenv, const double* __restrict__ gmask,
-    const double* __restrict__ ws, double* __restrict__ gtau, double* __restrict__ gx,
-    int32_t* __restrict__ gstatus) {
-  __shared__ __attribute__((aligned(16))) double sm[ipm_lds_doubles<D, SMALL, kRfOnly>()];
-  ipm_block<D, SMALL, false, kRfOnly>(P, static_cast<int>(blockIdx.x), nenv, gmask, ws, gtau, gx,
-                                   gstatus, nullptr, nullptr, 0, sm);
-}
-
-// Two models' interior point in one grid, one wavefront per SIMD (the one-wave variant of both):
-// blocks [0, nbA) are model A's wavefronts, the rest model B's.  The dispatcher hands out blocks
-// in order, so with the slower model first the faster model's wavefronts fill the SIMDs that
-// the first model's early finishers free (its iteration-count tail) -- two grids on two streams
-// instead split the SIMDs between the models and each pays its own tail.
-template <class DA, class DB, int RF = kRfNone>
-__global__ __launch_bounds__(kWave, 1) void osc_ipm_pair_kernel(PairArgs A, PairArgs B, int flags) {
-  __shared__ __attribute__((aligned(16))) double
-      sm[cmax(ipm_lds_doubles<DA, true, RF>(), ipm_lds_doubles<DB, true, RF>())];
-  const int nbA = (A.nenv + kEnvPerWave - 1) / kEnvPerWave;
-  const int blk = static_cast<int>(blockIdx.x);
-  // (flags bit 0: the cold fix-up pass over the envs left not OK, launched after the solve when
-  // refinement is fused -- a second launch: a second inlined body per model spills, launch_pair)
-  if (blk < nbA)
-    ipm_block<DA, true, false, RF>(A.P, blk, A.nenv, A.mask, A.ws, A.tau, A.x, A.status,
-                                   A.iters, nullptr, flags & 1, sm);
-  else
-    ipm_block<DB, true, false, RF>(B.P, blk - nbA, B.nenv, B.mask, B.ws, B.tau, B.x,
-                                   B.status, B.iters, nullptr, flags & 1, sm);
-}
-
-// ---- launch_ipm: the interior-point passes of one call (after the assembly) ----
-// All wavefronts resident at once (<= one per SIMD): the latency-optimised variant (one wave per
-// SIMD, Hr in LDS where it fits); otherwise the two-waves-per-SIMD variant.
-template <class D>
-void launch_ipm(const LaunchArgs& a) {
-  const osc_model* model = a.model;
-  const int32_t nenv = a.nenv;
-  const double* mask = a.mask;
-  double* ws = a.ws;
-  double *tau = a.tau, *x = a.x, *warm = a.warm;
-  int32_t *status = a.status, *iters = a.iters;
-  const hipStream_t s = a.s;
-  const unsigned nb = static_cast<unsigned>((nenv + kEnvPerWave - 1) / kEnvPerWave);
-  const int flags = a.y != nullptr ? 2 : 0;   // hand the multipliers to the dual kernel
-  if constexpr (D::WH) {
-    // wheel rows: the one-wave solve with the refinement fused; warm-started: the warm pass, then
-    // (same launch) the cold fix-up pass in the wavefronts holding an env the warm start left
-    // unconverged (the per-env status: the caller's array, else scratch -- launch_t).  The fused entries then run
-    // the active-set fallback over the envs the interior point left unconverged (launch_gi).
-    if (warm == nullptr) {
-      hipLaunchKernelGGL((osc_ipm_kernel<D, true, false, kRfFused>), dim3(nb), dim3(kWave), 0, s,
-                         model->dparams, nenv, mask, ws, tau, x, status, iters, nullptr, flags);
-    } else {
-      hipLaunchKernelGGL((osc_ipm_kernel<D, true, true, kRfFused>), dim3(nb), dim3(kWave), 0, s,
-                         model->dparams, nenv, mask, ws, tau, x, status, iters, warm, flags | 4);
-    }
-  } else {
-    // A warm-started solve is followed by a cold fix-up pass over the wavefronts that hold an
-    // env the warm start did not bring to convergence (per-env status: launch_t).
-    const bool small = nenv <= model->small_batch_max;
-    // Every cold solve runs the refinement in the same wavefront (kRfFused), and so does the
-    // one-wave warm solve; warm past one wave per SIMD the fused two-wave kernel spills (Go2
-    // 65,536 warm 50.0 -> 44.5 M solves/s), so that case keeps the separate refinement pass.
-    const bool fused = warm == nullptr && model->refine;
-    const bool fused_warm = small && warm != nullptr && model->refine;
-    // Lockstep compaction: more wavefronts than SIMDs, so the SIMD time the lockstep tail costs
-    // is time other wavefronts could use (ParkArgs; bitwise the single pass's results)
-    // (from four rounds of wavefronts per SIMD: at two, WaLTER configs[3] -- 8,192 tumbling envs,
-    // masks redrawn -- is 4 % slower with it, 17.0 vs 17.7 M solves/s; at eight, 32,768, 3 %
-    // faster: profiles/r03ze_*)
-    const bool compact = fused && model->park_it > 0 &&
-                         nenv >= kParkMinRounds * model->resident_envs &&
-                         static_cast<size_t>(nenv) * D::WS < (size_t{1} << 32);
-    if (warm == nullptr && compact) {
-      const WsLayout wl = ws_layout(model->kid, nenv);
-      char* base = reinterpret_cast<char*>(ws);
-      ParkArgs pa;
-      pa.park = reinterpret_cast<double*>(base + wl.park);
-      pa.list = reinterpret_cast<int32_t*>(base + wl.list);
-      pa.count = reinterpret_cast<int32_t*>(base + wl.count);
-      pa.park_it = model->park_it;
-      (void)hipMemsetAsync(pa.count, 0, sizeof(int32_t), s);
-      if (small) {
-        hipLaunchKernelGGL((osc_ipm_compact_kernel<D, true, kCpPark>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, flags, pa);
-        hipLaunchKernelGGL((osc_ipm_compact_kernel<D, true, kCpResume>), dim3(nb), dim3(kWave), 0,
-                           s, model->dparams, nenv, mask, ws, tau, x, status, iters, flags, pa);
-      } else {
-        hipLaunchKernelGGL((osc_ipm_compact_kernel<D, false, kCpPark>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, flags, pa);
-        hipLaunchKernelGGL((osc_ipm_compact_kernel<D, false, kCpResume>), dim3(nb), dim3(kWave), 0,
-                           s, model->dparams, nenv, mask, ws, tau, x, status, iters, flags, pa);
-      }
-      // the cold fix-up pass the one-launch solves run in their own launch (an env left not OK
-      // re-solved cold to mu <= 1e-12): here a third launch, whose wavefronts without such an
-      // env exit at once (round 5 census: 3 WaLTER envs in 1.6 M stalled at max_iter here)
-      if (small)
-        hipLaunchKernelGGL((osc_ipm_kernel<D, true, false, kRfFused>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, nullptr,
-                           (flags & 2) | 1);
-      else
-        hipLaunchKernelGGL((osc_ipm_kernel<D, false, false, kRfFused>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, nullptr,
-                           (flags & 2) | 1);
-    } else if (warm == nullptr) {
-      // every env the interior point or the refinement leaves not OK (MAX_ITER, UNREFINED,
-      // non-finite) is re-solved cold to mu <= 1e-12 by its own wavefront in the same launch, as
-      // the warm entries do (round 5's census: ~1 such env per 600,000 joint-state envs; only
-      // the wavefronts holding one run the second pass)
-      const int fl = flags | 4;
-      if (fused && small)
-        hipLaunchKernelGGL((osc_ipm_kernel<D, true, false, kRfFused>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, nullptr, fl);
-      else if (fused)
-        hipLaunchKernelGGL((osc_ipm_kernel<D, false, false, kRfFused>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, nullptr, fl);
-      else if (small)
-        hipLaunchKernelGGL((osc_ipm_kernel<D, true, false>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, nullptr, flags);
-      else
-        hipLaunchKernelGGL((osc_ipm_kernel<D, false, false>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, nullptr, flags);
-    } else if (fused_warm) {
-      // warm-started: the refinement runs in the same wavefront too, in the warm pass for the
-      // envs the warm start converged and in the cold fix-up pass (same launch) for the ones it
-      // redoes
-      hipLaunchKernelGGL((osc_ipm_kernel<D, true, true, kRfFused>), dim3(nb), dim3(kWave), 0, s,
-                         model->dparams, nenv, mask, ws, tau, x, status, iters, warm, 4);
-    } else {
-      // warm past one wave per SIMD (or without the refinement): the warm pass, the separate
-      // refinement pass, then the cold fix-up pass over every env not OK by then -- MAX_ITER,
-      // non-finite, and an env whose refinement found no KKT point, UNREFINED.  The
-      // fix-up pass runs the refinement in its own wavefront (the fused two-wave warm kernel: it
-      // spills, but only the wavefronts holding such an env execute it).
-      if (small)
-        hipLaunchKernelGGL((osc_ipm_kernel<D, true, true>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, warm, 0);
-      else
-        hipLaunchKernelGGL((osc_ipm_kernel<D, false, true>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, warm, 0);
-      if (model->refine) {
-        hipLaunchKernelGGL((osc_refine_kernel<D, false>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status);
-        hipLaunchKernelGGL((osc_ipm_kernel<D, false, true, kRfFused>), dim3(nb), dim3(kWave), 0,
-                           s, model->dparams, nenv, mask, ws, tau, x, status, iters, warm, 1);
-      } else if (small) {
-        hipLaunchKernelGGL((osc_ipm_kernel<D, true, true>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, warm, 1);
-      } else {
-        hipLaunchKernelGGL((osc_ipm_kernel<D, false, true>), dim3(nb), dim3(kWave), 0, s,
-                           model->dparams, nenv, mask, ws, tau, x, status, iters, warm, 1);
-      }
-    }
-  }
-}
-
 }  // namespace osc
+
+#include "osc_ipm_launch.hpp"

@@ -29,9 +29,8 @@ ARCH = os.environ.get("OSC_OFFLOAD_ARCH", "gfx950")
 SOURCES = ["osc_ipm_go2.hip", "osc_ipm_walter.hip", "osc_ipm_wheels.hip", "osc_multi.hip",
            "osc_setup.hip", "osc_gi.hip", "osc_dual.hip", "osc_kinematics.hip",
            "osc_producers.hip", "osc_api.hip", "osc_model.cpp", "osc_mjcf.cpp", "osc_host_feed.cpp"]
-HEADERS = ["osc_device.hpp", "osc_internal.hpp", "osc_setup.hpp", "osc_ipm.hpp", "osc_ipm_asm.hpp",
-           "osc_kin_device.hpp",
-           "osc_qpos.hpp", "osc_wave_sum.hpp"]
+# every header of csrc/ (the up-to-date check's dependency list: a new header is picked up by name)
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp"))
 # Per-unit compiler flags (variant builds may pass their own map to build()).  The interior-point
 # units use LLVM's iterative ILP scheduler (round 6): bitwise the same results, faster per solve
 # (profiles/r06/sched/); ldl_rows' column barrier keeps its schedule clear of DPP hazards

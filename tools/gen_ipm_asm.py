@@ -5,7 +5,7 @@ Why: a wavefront alone on its SIMD (the interior point at 4,096 Go2 envs) pays ~
 every instruction it issues, s_nop included (tools/mb/mb_issue.hip), and hipcc pads the boundary
 between two dependent inline-asm statements with an s_nop (its conservative forwarding-hazard rule
 for asm producers on gfx950).  The per-step asm statements of ldl_fwd_rows / ldl_bwd_rows /
-dot_rows (osc_ipm.hpp) cost an s_nop per step that way; one statement per solve, scheduled by
+dot_rows (osc_ipm_ldl.hpp) cost an s_nop per step that way; one statement per solve, scheduled by
 hand, needs none: each step's lane-mask compare is issued one step early (the mask's one wait
 state) and each DPP read of a value written by the previous step's FMA sits two instructions
 after it (the selects are the wait states).  Same instructions on the same values in the same
@@ -142,21 +142,21 @@ def main():
 def render():
     parts = [f"""// osc_ipm_asm.hpp -- GENERATED by tools/gen_ipm_asm.py (do not edit): the interior point's
 // triangular solves and Hr y product, one inline-asm statement each (see the generator's notes).
-// Included by osc_ipm.hpp; N = the reduced QP's size (24: unitree_go2, 32: walter_sr).
+// Included by osc_ipm_ldl.hpp; N = the reduced QP's size (24: unitree_go2, 32: walter_sr).
 #pragma once
 
 namespace osc {{
 
-// forward  z = L^-1 r over the factor ldl_rows leaves (osc_ipm.hpp ldl_fwd_rows): a0 / a1 in,
+// forward  z = L^-1 r over the factor ldl_rows leaves (osc_ipm_ldl.hpp ldl_fwd_rows): a0 / a1 in,
 // z0 / z1 (zero on entry) out
 template <int N>
 __device__ __forceinline__ void ldl_fwd_asm(const double (&c0)[N], const double (&c1)[N],
                                             double& a0, double& a1, double& z0, double& z1, int l);
-// backward (osc_ipm.hpp ldl_bwd_rows, before the 1 / D scaling): a0 / a1 in, z0 / z1 out
+// backward (osc_ipm_ldl.hpp ldl_bwd_rows, before the 1 / D scaling): a0 / a1 in, z0 / z1 out
 template <int N>
 __device__ __forceinline__ void ldl_bwd_asm(const double (&c0)[N], const double (&c1)[N],
                                             double& a0, double& a1, double& z0, double& z1, int l);
-// LDL^T in place (osc_ipm.hpp ldl_rows<N, true>): 1 / D_k to LDS at byte address addr + 8 k
+// LDL^T in place (osc_ipm_ldl.hpp ldl_rows<N, true>): 1 / D_k to LDS at byte address addr + 8 k
 template <int N>
 __device__ __forceinline__ void ldl_asm(double (&c0)[N], double (&c1)[N], double thr0, double thr1,
                                         int l, unsigned addr, double du);
@@ -179,7 +179,7 @@ __device__ __forceinline__ void dot_rows_asm(double& a, double& b, double& a2, d
 
 
 # ----------------------------------------------------------------------------------------------
-# LDL^T of the Newton matrix (osc_ipm.hpp ldl_rows, GUARD form) as one asm statement, scheduled
+# LDL^T of the Newton matrix (osc_ipm_ldl.hpp ldl_rows, GUARD form) as one asm statement, scheduled
 # by a small list scheduler: pivot k+1's preparation (test, broadcast, reciprocal, scaling, the
 # next multipliers) is interleaved with pivot k's trailing FMAs so that every wait state the
 # hardware needs is an FMA instead of an s_nop.  Temporaries whose 32-bit halves the selects
@@ -207,7 +207,7 @@ def ldl_prep(k, n):
     G, D, R = SCR["G"], SCR["D"], SCR["R"]
     S = f"S{k % 2}"
     Sr = SCR[S]
-    # slot 0: the pivot gets the torque rows' diagonal term du (osc_ipm.hpp ldl_rows)
+    # slot 0: the pivot gets the torque rows' diagonal term du (osc_ipm_ldl.hpp ldl_rows)
     first = (Ins(f"v_add_f64 v[{G}:{G + 1}], {r64(own)}, %[du]", w=["G"], r=[own, "du"]) if s == 0
              else Ins(f"v_mov_b64 v[{G}:{G + 1}], {r64(own)}", w=["G"], r=[own]))
     p = [first,

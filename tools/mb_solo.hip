@@ -50,7 +50,7 @@ __global__ __launch_bounds__(64, 1) void k_a(double* out, unsigned long long* cl
     double d0, d1;
     __builtin_amdgcn_s_waitcnt(0);
     const unsigned long long t0 = clock64();
-    ldl_rows<N>(c0, c1, sdinv[grp], l, d0, d1, 1e-13 * k0[l], 1e-13 * k1[j1]);
+    ldl_rows<N>(c0, c1, sdinv[grp], l, d0, d1, 1e-13 * k0[l], 1e-13 * k1[j1], 0.0);
     const unsigned long long t1 = clock64();
     double a0 = 1.0 + l, a1 = 2.0 + l;
     ldl_solve_rows<N>(c0, c1, d0, d1, a0, a1, l);
