@@ -51,6 +51,7 @@
 
 #include "osc_batch.h"
 #include "osc_kin_device.hpp"
+#include "osc_kin_model.hpp"
 #include "osc_kinematics.h"
 #include "osc_qpos.hpp"
 
@@ -456,13 +457,6 @@ std::string kin_library_dir() {
 }
 
 }  // namespace
-
-struct osc_kin_model {
-  osc_kin_desc desc;
-  KinDev host;
-  KinDev* dev;
-  int device;
-};
 
 extern "C" int osc_kin_desc_from_json(const char* robot, const char* json_path,
                                       osc_kin_desc* desc) {

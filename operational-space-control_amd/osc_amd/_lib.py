@@ -39,6 +39,12 @@ EXPORTED_SYMBOLS = ("osc_desc_from_yaml", "osc_model_create", "osc_model_create_
                     "osc_host_feed_create", "osc_host_feed_destroy", "osc_host_feed_inputs",
                     "osc_host_feed_submit", "osc_host_feed_wait", "osc_host_feed_timing")
 
+# include/osc_rollout.h.  Kept apart from EXPORTED_SYMBOLS, which tests/test_abi.py pins to the
+# declarations of the four headers it reads; tests/test_rollout_ref.py pins this list likewise.
+ROLLOUT_SYMBOLS = ("osc_batch_integrate", "osc_rollout_workspace_bytes", "osc_batch_rollout")
+ROLLOUT_WARM = 1
+ROLLOUT_TARGETS_HELD, ROLLOUT_TARGETS_PD_BASE = 0, 1
+
 OSC_KIN_MAX_BODIES = 16
 OSC_KIN_MAX_DOFS = 32
 OSC_KIN_MAX_SITES = 32
@@ -131,6 +137,18 @@ class OscFeedTiming(ctypes.Structure):
     """osc_feed_timing (include/osc_host_feed.h): per-stage HIP-event durations (ms)."""
     _fields_ = [(n, ctypes.c_float) for n in ("h2d_ms", "solve_ms", "d2h_ms",
                                                "h2d_start_to_d2h_end_ms", "kin_ms")]
+
+
+class OscRolloutArgs(ctypes.Structure):
+    """osc_rollout_args (include/osc_rollout.h)."""
+    _fields_ = [("nticks", ctypes.c_int32), ("dt", ctypes.c_double), ("flags", ctypes.c_uint32),
+                ("target_mode", ctypes.c_int32), ("T", ctypes.c_void_p),
+                ("pos_ref", ctypes.c_void_p), ("pos_ref_per_env", ctypes.c_int32),
+                ("quat_ref", ctypes.c_void_p), ("quat_ref_per_env", ctypes.c_int32),
+                ("gains", ctypes.c_double * 4)] + \
+        [(n, ctypes.c_void_p) for n in ("contact_mask", "qpos", "qvel", "tau", "qpos_hist",
+                                         "qvel_hist", "tau_hist", "status_hist", "bad_ticks",
+                                         "workspace")] + [("workspace_bytes", ctypes.c_size_t)]
 
 
 FEED_QP, FEED_JOINT_STATES, FEED_WARM = 0, 1, 1
@@ -245,6 +263,13 @@ def lib() -> ctypes.CDLL:
     L.osc_batch_solve_qpos_warm.argtypes = [vp, vp, i32] + [vp] * 9 + [ctypes.c_size_t, vp,
                                                                       ctypes.c_size_t, vp]
     L.osc_batch_solve_qpos_warm.restype = ctypes.c_int
+    L.osc_batch_integrate.argtypes = [vp, i32, ctypes.c_double, vp, ctypes.c_int64, vp, vp, vp,
+                                      vp, vp]
+    L.osc_batch_integrate.restype = ctypes.c_int
+    L.osc_rollout_workspace_bytes.argtypes = [vp, vp, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    L.osc_rollout_workspace_bytes.restype = ctypes.c_int
+    L.osc_batch_rollout.argtypes = [vp, vp, i32, ctypes.POINTER(OscRolloutArgs), vp]
+    L.osc_batch_rollout.restype = ctypes.c_int
     L.osc_host_feed_create.argtypes = [vp, vp, i32, i32, ctypes.c_uint32, i32, ctypes.POINTER(vp)]
     L.osc_host_feed_create.restype = ctypes.c_int
     L.osc_host_feed_destroy.argtypes = [vp]

@@ -8,6 +8,9 @@ Reference interface this mirrors (paths relative to the reference's operational-
          OSCBatchSolver.solve
   * the whole tick (update_mj_data .. solve_optimization, :546-573)
       -> KinematicsBatch.solve(solver, qpos, qvel, T, mask)   (osc_batch_solve_qpos)
+Beyond the reference (include/osc_rollout.h): KinematicsBatch.rollout(...) runs K closed-loop
+ticks on the device by integrating the QP's own acceleration (an idealised rollout over the
+controller's model, not a simulator), KinematicsBatch.integrate_into(...) is its step alone.
 The kinematic tree comes from operational-space-control_amd/config/<robot>_kinematics.json
 (illustrative trees: the reference's MJCF files are not vendored) or from any osc_kin_desc.
 Launches go through the C-ABI on the current torch stream; there is no CPU fallback.
@@ -183,6 +186,118 @@ class KinematicsBatch:
                          device=self.device)
         with torch.cuda.device(self.device):
             return self.solve_into(solver, out, qpos, qvel, T, mask, ws)
+
+    # ---- closed-loop rollout over the controller's own model (include/osc_rollout.h) ----
+
+    def integrate_into(self, qpos, qvel, qacc, dt, status=None, bad_ticks=None, stream=None):
+        """osc_batch_integrate, in place on device tensors: qvel += dt qacc, then qpos =
+        integratePos(qpos, qvel, dt).  qacc (nenv, nv) may be a strided view with contiguous rows,
+        such as x[:, :nv] of a solve; an env whose status is OSC_SOLVE_NUMERICAL or whose qacc is
+        not finite is left unchanged and counted in bad_ticks (int32), as every not-OK status is."""
+        nenv = int(qpos.shape[0])
+        if qacc.dim() != 2 or tuple(qacc.shape) != (nenv, self.nv) or \
+                (self.nv > 1 and qacc.stride(1) != 1):
+            raise ValueError(f"qacc: expected (nenv, {self.nv}) with contiguous rows")
+        for name, t, dt_ in (("qpos", qpos, torch.float64), ("qvel", qvel, torch.float64),
+                             ("qacc", qacc, torch.float64), ("status", status, torch.int32),
+                             ("bad_ticks", bad_ticks, torch.int32)):
+            if t is not None and (t.dtype != dt_ or t.device != self.device):
+                raise ValueError(f"{name}: expected a {dt_} tensor on {self.device}")
+        if not (qpos.is_contiguous() and qvel.is_contiguous()):
+            raise ValueError("qpos / qvel: contiguous tensors required (updated in place)")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = _lib.lib().osc_batch_integrate(
+            self._h, nenv, float(dt), ptr(qacc), qacc.stride(0) if nenv > 1 else self.nv,
+            ptr(status), ptr(qpos), ptr(qvel), ptr(bad_ticks),
+            ctypes.c_void_p(self._stream(stream, self.device)))
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_integrate", rc)
+        return qpos, qvel
+
+    def rollout_workspace_bytes(self, solver, nenv: int, nticks: int) -> int:
+        nb = ctypes.c_size_t()
+        rc = _lib.lib().osc_rollout_workspace_bytes(solver._h, self._h, nenv, nticks,
+                                                    ctypes.byref(nb))
+        if rc != 0:
+            raise _lib.OSCError("osc_rollout_workspace_bytes", rc)
+        return nb.value
+
+    def rollout(self, solver, qpos, qvel, mask, nticks: int, dt: float, T=None, pd=None,
+                warm: bool = True, history: bool = False, stream=None,
+                workspace="alloc") -> "RolloutResult":
+        """osc_batch_rollout: nticks ticks of kinematics -> targets -> solve -> step on the
+        device, one enqueue, no host sync.  An idealised rollout over the controller's model, not
+        a simulator: no ground, no contact detection, `mask` held constant.
+        Exactly one of T (nenv, ns, 6), targets held over the rollout, and pd = (pos_ref,
+        quat_ref, gains), osc_pd_base_targets of the current state every tick (references (3,) /
+        (4,) shared or (nenv, 3) / (nenv, 4) per env; gains (kp_lin, kd_lin, kp_ang, kd_ang)).
+        Inputs (torch tensors or numpy arrays) are copied: the caller's arrays are not modified.
+        workspace: "alloc" = a tensor of rollout_workspace_bytes, None = the library's
+        stream-ordered scratch, or a float64 device tensor."""
+        if (T is None) == (pd is None):
+            raise ValueError("exactly one of T and pd must be given")
+        d = solver.dims
+        nenv, nticks = int(qpos.shape[0]), int(nticks)
+        o = dict(device=self.device, dtype=torch.float64)
+        qpos = self._dev(qpos, (nenv, self.nq), "qpos").clone()
+        qvel = self._dev(qvel, (nenv, self.nv), "qvel").clone()
+        mask = self._dev(mask, (nenv, d["nc"]), "mask")
+        a = _lib.OscRolloutArgs()
+        a.nticks, a.dt, a.flags = nticks, float(dt), _lib.ROLLOUT_WARM if warm else 0
+        keep = [qpos, qvel, mask]
+        if T is not None:
+            T = self._dev(T, (nenv, d["ns"], 6), "T")
+            a.target_mode, a.T = _lib.ROLLOUT_TARGETS_HELD, T.data_ptr()
+            keep.append(T)
+        else:
+            pos_ref, quat_ref, gains = pd
+            pos_ref, quat_ref = (r if isinstance(r, torch.Tensor) else
+                                 np.asarray(r, dtype=np.float64) for r in (pos_ref, quat_ref))
+            per_env = [int(r.ndim == 2) for r in (pos_ref, quat_ref)]
+            pos_ref = self._dev(pos_ref, (nenv, 3) if per_env[0] else (3,), "pos_ref")
+            quat_ref = self._dev(quat_ref, (nenv, 4) if per_env[1] else (4,), "quat_ref")
+            a.target_mode = _lib.ROLLOUT_TARGETS_PD_BASE
+            a.pos_ref, a.pos_ref_per_env = pos_ref.data_ptr(), per_env[0]
+            a.quat_ref, a.quat_ref_per_env = quat_ref.data_ptr(), per_env[1]
+            a.gains[:] = [float(g) for g in gains]
+            keep += [pos_ref, quat_ref]
+        res = RolloutResult(qpos, qvel, torch.zeros((nenv, d["nu"]), **o),
+                            torch.zeros((nenv,), device=self.device, dtype=torch.int32))
+        nslab = max(nticks, 0)
+        if history:
+            res.qpos_hist = torch.zeros((nslab + 1, nenv, self.nq), **o)
+            res.qvel_hist = torch.zeros((nslab + 1, nenv, self.nv), **o)
+            res.tau_hist = torch.zeros((nslab, nenv, d["nu"]), **o)
+            res.status_hist = torch.zeros((nslab, nenv), device=self.device, dtype=torch.int32)
+            a.qpos_hist, a.qvel_hist = res.qpos_hist.data_ptr(), res.qvel_hist.data_ptr()
+            a.tau_hist, a.status_hist = res.tau_hist.data_ptr(), res.status_hist.data_ptr()
+        if isinstance(workspace, str):
+            workspace = torch.empty((max(self.rollout_workspace_bytes(solver, nenv, nslab) // 8,
+                                         2),), **o)
+        if workspace is not None:
+            a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
+        a.contact_mask, a.qpos, a.qvel = mask.data_ptr(), qpos.data_ptr(), qvel.data_ptr()
+        a.tau, a.bad_ticks = res.tau.data_ptr(), res.bad_ticks.data_ptr()
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().osc_batch_rollout(solver._h, self._h, nenv, ctypes.byref(a),
+                                              ctypes.c_void_p(self._stream(stream, self.device)))
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_rollout", rc)
+        res._keep = keep + [workspace]   # inputs and scratch stay alive until the stream is done
+        return res
+
+
+@dataclasses.dataclass
+class RolloutResult:
+    qpos: torch.Tensor                        # (nenv, nq) state after the last tick
+    qvel: torch.Tensor                        # (nenv, nv)
+    tau: torch.Tensor                         # (nenv, nu) the last tick's torques
+    bad_ticks: torch.Tensor                   # (nenv,) int32: ticks whose solve was not OK
+    qpos_hist: torch.Tensor | None = None     # (nticks + 1, nenv, nq), slab 0 = the initial state
+    qvel_hist: torch.Tensor | None = None     # (nticks + 1, nenv, nv)
+    tau_hist: torch.Tensor | None = None      # (nticks, nenv, nu)
+    status_hist: torch.Tensor | None = None   # (nticks, nenv) int32
+    _keep: list | None = None
 
 
 def _tree_joints(tree: dict):
