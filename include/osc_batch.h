@@ -111,8 +111,9 @@ typedef struct {
   double w_rot[OSC_MAX_SITES];    /* <site>_rotational_tracking                               */
   double w_torque;                /* weights_config.torque                                    */
   double w_reg;                   /* weights_config.regularization                            */
-  double u_lb[OSC_MAX_NU];        /* torque bounds (osc.h:285-296)                            */
-  double u_ub[OSC_MAX_NU];
+  double u_lb[OSC_MAX_NU];        /* torque bounds (osc.h:285-296); u_lb[i] < u_ub[i] strictly */
+  double u_ub[OSC_MAX_NU];        /*   (a pinned torque, u_lb == u_ub, leaves the interior    */
+                                  /*   point no interior: OSC_ERR_INVALID_ARGUMENT)           */
   double z_lb[3];                 /* per-contact force bounds before the mask multiply        */
   double z_ub[3];                 /*   (osc.h:297-308): {-inf,-inf,0} / {inf,inf,big_number}  */
   double infinity;                /* OSQP_INFTY (1e30); |bound| >= infinity/1e10 = no bound   */

@@ -130,8 +130,10 @@ extern "C" int osc_model_create_tuned(const osc_model_desc* desc, const osc_mode
   for (int c = 0; c < 2; ++c)
     if (std::fabs(d.z_lb[c]) < thresh || std::fabs(d.z_ub[c]) < thresh)
       return OSC_ERR_INVALID_ARGUMENT;
+  // u_lb == u_ub pins the torque: a box without interior, where the interior point has no
+  // strictly feasible slack pair to start from (measured: MAX_ITER on some envs).  Refused.
   for (int i = 0; i < d.nu; ++i)
-    if (!(d.u_lb[i] <= d.u_ub[i])) return OSC_ERR_INVALID_ARGUMENT;
+    if (!(d.u_lb[i] < d.u_ub[i])) return OSC_ERR_INVALID_ARGUMENT;
   if (d.wheel_rows != 0 && d.wheel_rows != 1) return OSC_ERR_INVALID_ARGUMENT;
   for (int i = 0; d.wheel_rows && i < d.nc; ++i)
     if (d.wheel_dof[i] < -1 || d.wheel_dof[i] >= d.nv || !std::isfinite(d.wheel_radius[i]))

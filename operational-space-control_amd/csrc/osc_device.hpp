@@ -68,6 +68,11 @@ struct DevParams {
 // Full-space refinement: at most kRefineRounds active-set rounds of at most kRefineMaxSteps
 // steps each (osc_ipm.hpp; the host clamps osc_model_tuning.refine_steps to the latter).
 constexpr int kRefineRounds = 8, kRefineMaxSteps = 8;
+// Interior point: an env whose largest multiplier is above this is not re-centred to unit
+// multipliers at restart_iter / warm_restart (osc_ipm.hpp).  Between the two populations
+// measured with the numpy model of the kernel: <= 25 on the shipped models' stalled envs,
+// >= 3.7e6 on the envs a re-centre throws back (tests/desc_variants.py: tight, lifted).
+constexpr double kRecentreLamMax = 1e3;
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int even(int a) { return (a + 1) & ~1; }   // keep LDS/workspace regions 16-B aligned

@@ -454,6 +454,10 @@ __global__ __launch_bounds__(kWave, 2) void osc_dual_kernel(
       const int c = r - NV - NW - 4 * NC;   // design variable of the box row
       if (c >= NV && c < NV + NU) {
         v = sg[NB + c - NV] - wu * x[c];
+        // a side the model switches off carries no multiplier: the stationarity residue of an
+        // inactive or one-sided torque (design-vector rounding, either sign) stays off it
+        const bool hi = fabs(P->u_ub[c - NV]) < P->inf_thresh, lo = fabs(P->u_lb[c - NV]) < P->inf_thresh;
+        if ((v > 0.0 && !hi) || (v < 0.0 && !lo)) v = 0.0;
       } else if (c >= NV + NU) {
         const int zc = c - NV - NU, k = zc / 3;
         if (mask[k] == 0.0) v = -sr[zc];

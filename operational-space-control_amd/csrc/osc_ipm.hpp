@@ -473,12 +473,21 @@ __device__ __forceinline__ void ipm_block(
     // round-3 warm-stall study) then finish ~10 iterations later instead of at max_iter.  No env of
     // the fresh-batch sweeps is still that far off at iteration 20 (tools/ipm_model.py
     // "recenter20": identical iteration counts).
+    // Unit multipliers are a fresh start only where the iterate's own are of that scale (the
+    // stalled envs of the censuses: largest multiplier <= 25).  A model whose bounds cut deep into
+    // the tracking objective (torque boxes of a few N m, an fz cap of tens of N) has multipliers
+    // of 1e6-1e8; the unit-scale cold start takes ~25 iterations to climb there and the env is a
+    // few full steps from its optimum at `restart_iter` -- re-centred, it is thrown back to the
+    // start and ends at max_iter (tests/test_gpu_descriptors.py).  Such an env keeps its iterate.
     bool restart = false;
     if (it == restart_iter || (WARM && any_warm && it == warm_restart)) {
-      double cr = 0.0;
+      double cr = 0.0, lmax = 0.0;
 #pragma unroll
-      for (int t = 0; t < NRL; ++t) cr += act[t] ? s[t] * lam[t] : 0.0;
-      const bool far = row_sum(cr) / fmax(m_act, 1.0) > 1e-6;
+      for (int t = 0; t < NRL; ++t) {
+        cr += act[t] ? s[t] * lam[t] : 0.0;
+        lmax = fmax(lmax, lam[t]);   // (inactive rows hold lambda = 0)
+      }
+      const bool far = row_sum(cr) / fmax(m_act, 1.0) > 1e-6 && row_max(lmax) <= kRecentreLamMax;
       const bool mine = far && !done && it == (warm ? warm_restart : restart_iter);
       restart = __ballot(mine) != 0;
       if (restart) wave_sync();

@@ -40,9 +40,12 @@ class SolveResult:
 class OSCBatchSolver:
     def __init__(self, robot: str, yaml_path: str | None = None, eps_mu: float | None = None,
                  max_iter: int | None = None, device: torch.device | int | None = None,
-                 tuning: dict | None = None):
+                 tuning: dict | None = None, desc_overrides: dict | None = None):
         """tuning: fields of osc_model_tuning (include/osc_batch.h) to change from the model's
-        defaults, e.g. {"small_batch_max": 0} (solver policy only, never the QP)."""
+        defaults, e.g. {"small_batch_max": 0} (solver policy only, never the QP).
+        desc_overrides: fields of osc_model_desc to change after the YAML is read -- these DO
+        change the QP -- e.g. {"mu": 0.35, "u_lb": [-3.0] * 12, "z_ub": [1e30, 1e30, 30.0]}; an
+        array field takes a sequence that replaces its leading entries."""
         if not torch.cuda.is_available():
             raise RuntimeError("OSCBatchSolver needs a HIP device (no CPU fallback exists)")
         self.robot = robot
@@ -54,6 +57,17 @@ class OSCBatchSolver:
             desc.eps_mu = float(eps_mu)
         if max_iter is not None:
             desc.max_iter = int(max_iter)
+        for k, v in (desc_overrides or {}).items():
+            if k not in dict(_lib.OscModelDesc._fields_):
+                raise KeyError(f"osc_model_desc has no field {k!r}")
+            field = getattr(desc, k)
+            if isinstance(field, ctypes.Array):
+                v = list(v)
+                if len(v) > len(field):
+                    raise ValueError(f"{k}: at most {len(field)} values, got {len(v)}")
+                field[:len(v)] = v
+            else:
+                setattr(desc, k, v)
         self.desc = desc
         self.wheels = desc.wheel_rows != 0
         tune = _lib.OscModelTuning()

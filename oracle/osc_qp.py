@@ -114,6 +114,13 @@ class OSCModel:
     u_lb: np.ndarray
     u_ub: np.ndarray
     site_dofs: list
+    # per-contact force bounds before the mask multiply and the "no bound" value; the defaults
+    # are the reference's constants (operational_space_controller.h:276-308)
+    z_lb: np.ndarray = dataclasses.field(
+        default_factory=lambda: np.array([-OSQP_INFTY, -OSQP_INFTY, 0.0]))
+    z_ub: np.ndarray = dataclasses.field(
+        default_factory=lambda: np.array([OSQP_INFTY, OSQP_INFTY, BIG_NUMBER]))
+    infinity: float = OSQP_INFTY
 
     @property
     def nz(self):
@@ -132,7 +139,15 @@ class OSCModel:
         return 6 * self.ns
 
 
-def load_model(robot: str, yaml_path: str | None = None) -> OSCModel:
+# osc_model_desc fields (include/osc_batch.h) an override dict may set
+_OVERRIDABLE = ("mu", "w_pos", "w_rot", "w_torque", "w_reg", "u_lb", "u_ub", "z_lb", "z_ub",
+                "infinity")
+
+
+def load_model(robot: str, yaml_path: str | None = None, overrides: dict | None = None) -> OSCModel:
+    """overrides: osc_model_desc field -> value applied after the YAML (array fields take
+    sequences of the model's own length), as OSCBatchSolver(desc_overrides=...) does on the
+    library's side; an unknown field raises KeyError."""
     r = ROBOTS[robot]
     path = yaml_path or os.path.join(_PKG_CONFIG, r["config"])
     with open(path, "r") as fh:
@@ -145,11 +160,23 @@ def load_model(robot: str, yaml_path: str | None = None) -> OSCModel:
     assert len(cfg["contact_site_list"]) == r["nc"]
     w_pos = np.array([float(w[f"{k}_translational_tracking"]) for k in r["site_keys"]])
     w_rot = np.array([float(w[f"{k}_rotational_tracking"]) for k in r["site_keys"]])
-    return OSCModel(name=robot, nv=r["nv"], nu=r["nu"], nc=r["nc"], ns=ns,
-                    mu=float(cfg["friction_coefficient"]), w_pos=w_pos, w_rot=w_rot,
-                    w_torque=float(w["torque"]), w_reg=float(w["regularization"]),
-                    u_lb=np.array(r["u_lb"], float), u_ub=np.array(r["u_ub"], float),
-                    site_dofs=r["site_dofs"])
+    model = OSCModel(name=robot, nv=r["nv"], nu=r["nu"], nc=r["nc"], ns=ns,
+                     mu=float(cfg["friction_coefficient"]), w_pos=w_pos, w_rot=w_rot,
+                     w_torque=float(w["torque"]), w_reg=float(w["regularization"]),
+                     u_lb=np.array(r["u_lb"], float), u_ub=np.array(r["u_ub"], float),
+                     site_dofs=r["site_dofs"])
+    for k, v in (overrides or {}).items():
+        if k not in _OVERRIDABLE:
+            raise KeyError(f"osc_model_desc has no overridable field {k!r}")
+        old = getattr(model, k)
+        if isinstance(old, np.ndarray):
+            v = np.array(v, float)
+            if v.shape != old.shape:
+                raise ValueError(f"{k}: expected {old.shape[0]} values, got {v.shape}")
+            setattr(model, k, v)
+        else:
+            setattr(model, k, float(v))
+    return model
 
 
 def task_weights(model: OSCModel) -> np.ndarray:
@@ -280,12 +307,13 @@ def build_qp(model: OSCModel, M, C, J, b, T, mask, wheel: WheelRows | None = Non
     Aeq_all = Aeq if Aw is None else np.vstack([Aeq, Aw])
     beq_all = beq if bw is None else np.concatenate([beq, bw])
     A = np.vstack([Aeq_all, Aineq, np.eye(n)])
-    z_lb = np.tile([-OSQP_INFTY, -OSQP_INFTY, 0.0], model.nc)
-    z_ub = np.tile([OSQP_INFTY, OSQP_INFTY, BIG_NUMBER], model.nc)
+    inf = model.infinity
+    z_lb = np.tile(model.z_lb, model.nc)
+    z_ub = np.tile(model.z_ub, model.nc)
     mrep = np.repeat(mask, 3)
-    l = np.concatenate([beq_all, np.full(4 * model.nc, -OSQP_INFTY), np.full(nv, -OSQP_INFTY),
+    l = np.concatenate([beq_all, np.full(4 * model.nc, -inf), np.full(nv, -inf),
                         model.u_lb, z_lb * mrep])
-    u = np.concatenate([beq_all, bineq, np.full(nv, OSQP_INFTY), model.u_ub, z_ub * mrep])
+    u = np.concatenate([beq_all, bineq, np.full(nv, inf), model.u_ub, z_ub * mrep])
     return QPData(H, f, Aeq, beq, Aineq, bineq, A, l, u, Aw, bw)
 
 

@@ -83,17 +83,24 @@ def _independent(A, eq):
 
 
 def _feasible_start(model: OSCModel, qp: QPData, M, C, J):
-    """Strictly interior point for every one-sided row (u mid-box, z = (0, 0, fz0))."""
+    """Strictly interior point for every one-sided row of any box: a torque at 0 where 0 is
+    strictly inside its box, else mid-box, or 1 inside the finite side of a one-sided box (a
+    bound at +-infinity has no midpoint); z = (0, 0, fz0) with fz0 = lo + min(1, (hi - lo) / 2),
+    above an fz lower bound of any size."""
     nv, nu, nz = model.nv, model.nu, model.nz
     off_u = qp.A.shape[0] - model.n + nv
     off_z = off_u + nu
     lu, uu = qp.l[off_u:off_u + nu], qp.u[off_u:off_u + nu]
-    u0 = np.where((lu < 0) & (uu > 0), 0.0, 0.5 * (lu + uu))
+    lo_fin, hi_fin = lu > -INF_THRESH, uu < INF_THRESH
+    with np.errstate(invalid="ignore", over="ignore"):
+        mid = 0.5 * (lu + uu)
+    u0 = np.where(lo_fin & hi_fin, mid, np.where(lo_fin, lu + 1.0, np.where(hi_fin, uu - 1.0, 0.0)))
+    u0 = np.where((lu < 0) & (uu > 0), 0.0, u0)
     z0 = np.zeros(nz)
     for k in range(model.nc):
         lo, hi = qp.l[off_z + 3 * k + 2], qp.u[off_z + 3 * k + 2]
         if lo != hi:
-            z0[3 * k + 2] = min(1.0, 0.5 * (lo + hi))
+            z0[3 * k + 2] = lo + min(1.0, 0.5 * (hi - lo))
     rhs = b_matrix(model) @ u0 + contact_jacobian(model, J) @ z0 - np.asarray(C).reshape(-1)
     dv0 = np.linalg.solve(np.asarray(M).reshape(nv, nv), rhs)
     return np.concatenate([dv0, u0, z0])

@@ -140,6 +140,32 @@ def test_wheel_no_slip_yaml_keys(tmp_path):
     assert _lib.lib().osc_model_create(ctypes.byref(d), ctypes.byref(h)) == 1
 
 
+@pytest.mark.parametrize("robot", ["unitree_go2", "walter_sr"])
+def test_pinned_actuator_refused(robot):
+    """u_lb[i] == u_ub[i] leaves the torque box without an interior, which the interior point
+    needs: with the `tight` model of tests/desc_variants.py and u_lb[2] == u_ub[2] == 1.5 one of
+    61 WaLTER envs came back OSC_SOLVE_MAX_ITER on an MI355X (the others OK and at the oracle's
+    optimum; never a wrong OK).  The model is refused at creation, ahead of any device call; the
+    same descriptor with the box opened by one ulp passes the validation."""
+    L = _lib.lib()
+    h = ctypes.c_void_p()
+    for tuned in (False, True):
+        d = _lib.desc_from_yaml(robot)
+        t = _lib.OscModelTuning()
+        assert L.osc_model_tuning_defaults(ctypes.byref(d), ctypes.byref(t)) == 0
+        create = (lambda: L.osc_model_create_tuned(ctypes.byref(d), ctypes.byref(t), ctypes.byref(h))) \
+            if tuned else (lambda: L.osc_model_create(ctypes.byref(d), ctypes.byref(h)))
+        d.u_lb[2] = d.u_ub[2] = 1.5
+        assert create() == 1
+        d.u_ub[2] = np.nextafter(1.5, 2.0)
+        rc = create()
+        assert rc in (0, 5), rc          # valid: created, or OSC_ERR_NO_DEVICE on a CPU-only host
+        if rc == 0:
+            L.osc_model_destroy(h)
+        d.u_lb[2], d.u_ub[2] = 2.0, 1.5   # (and a crossed box, as before)
+        assert create() == 1
+
+
 def test_error_codes():
     L = _lib.lib()
     d = _lib.OscModelDesc()

@@ -43,12 +43,18 @@ def unpack_hr(block, ny):
                                              ("unitree_go2", "zeros")])
 def test_reduced_qp_consistent_with_oracle_qp(gpu, robot, mask_mode):
     from osc_amd.solver import OSCBatchSolver
-    s = OSCBatchSolver(robot)
+    inp = generate(robot, 16, SEED_BASE + 31, "tumbling", mask_mode)
+    check_reduced_qp(gpu, OSCBatchSolver(robot), load_model(robot), inp)
+
+
+def check_reduced_qp(gpu, s, model, inp):
+    """The reduced QP the solver `s` assembles for the batch `inp` against the oracle's full QP
+    of `model` (the same model as s's descriptor; tests/test_gpu_descriptors.py passes others)."""
+    robot = s.robot
     d = dims(robot)
     nv, nu, nc, nz = d["nv"], d["nu"], d["nc"], d["nz"]
     nb, ny = nv - nu, nu + nz
-    nenv = 16
-    inp = generate(robot, nenv, SEED_BASE + 31, "tumbling", mask_mode)
+    nenv = inp["M"].shape[0]
     args = s.prepare(**inp)
     L = _lib.lib()
     nbytes, ebytes = ctypes.c_size_t(), ctypes.c_size_t()
@@ -80,7 +86,6 @@ def test_reduced_qp_consistent_with_oracle_qp(gpu, robot, mask_mode):
     assert rc == 0
     torch.cuda.synchronize()
     D = dbg.cpu().numpy()[:nenv * sz].reshape(nenv, sz)
-    model = load_model(robot)
     rng = np.random.default_rng(0)
     for e in range(nenv):
         Hr = unpack_hr(D[e, o_hr:o_hr + hr_size], ny)

@@ -22,7 +22,7 @@ torch = pytest.importorskip("torch")
 
 from osc_amd.robots import config_path, dims
 from osc_amd.synth import SEED_BASE, WALTER_WHEEL_DOFS, WHEEL_RADIUS, generate, wheel_directions
-from osc_qp import BIG_NUMBER, WheelRows, build_qp, load_model, torque
+from osc_qp import OSCModel, WheelRows, build_qp, load_model, torque
 from qp_exact import solve_exact
 
 pytestmark = pytest.mark.gpu
@@ -178,8 +178,9 @@ def test_wheel_model_entry_points(gpu):
 # ---------------------------------------------------------------------------- duals / KKT
 def _batched_qp(robot, M, C, J, b, T, mask, wheel=None, wd=None):
     """The reference QP of oracle/osc_qp.build_qp for a whole batch, on the GPU (torch fp64):
-    H, f, A = [Aeq (; Aw); Aineq; I], l, u."""
-    m = load_model(robot)
+    H, f, A = [Aeq (; Aw); Aineq; I], l, u.  `robot`: a shipped model's name, or an OSCModel (its
+    own weights, friction, bounds and infinity: tests/test_gpu_descriptors.py)."""
+    m = robot if isinstance(robot, OSCModel) else load_model(robot)
     nv, nu, nz, n, nc, ns = m.nv, m.nu, m.nz, m.n, m.nc, m.ns
     dev, E = M.device, M.shape[0]
     W = torch.as_tensor(np.concatenate([np.repeat(m.w_pos, 3), np.repeat(m.w_rot, 3)]), device=dev)
@@ -220,10 +221,10 @@ def _batched_qp(robot, M, C, J, b, T, mask, wheel=None, wd=None):
             Ain[:, 4 * k + r, nv + nu + 3 * k:nv + nu + 3 * k + 3] = torch.tensor(
                 [sx, sy, -m.mu], dtype=torch.float64, device=dev)
     rows += [Ain, torch.eye(n, dtype=torch.float64, device=dev).expand(E, n, n)]
-    inf = 1e30
+    inf = m.infinity
     mrep = mask.repeat_interleave(3, dim=1)
-    zlb = torch.tensor([-inf, -inf, 0.0] * nc, dtype=torch.float64, device=dev)
-    zub = torch.tensor([inf, inf, BIG_NUMBER] * nc, dtype=torch.float64, device=dev)
+    zlb = torch.as_tensor(np.tile(m.z_lb, nc), dtype=torch.float64, device=dev)
+    zub = torch.as_tensor(np.tile(m.z_ub, nc), dtype=torch.float64, device=dev)
     full = lambda v: torch.full((E, v[0]), v[1], dtype=torch.float64, device=dev)
     lo += [full((4 * nc, -inf)), full((nv, -inf)),
            torch.as_tensor(m.u_lb, device=dev).expand(E, nu), zlb * mrep]

@@ -220,7 +220,10 @@ def ipm(Hr, g, G, h, eps_mu=1e-12, max_iter=40, variant=(), init=None):
     last_du = None
     for it in range(max_iter + 1):
         for v in variant:
-            if v.startswith("recenter") and it == int(v[8:]) and s @ lam / m > 1e-6:
+            # (the kernel's rule: not where the iterate's multipliers are far above the unit ones
+            # the re-centre would put in their place, kRecentreLamMax in osc_device.hpp)
+            if v.startswith("recenter") and it == int(v[8:]) and s @ lam / m > 1e-6 \
+                    and lam.max() <= 1e3:
                 s = np.maximum(h - G @ y, 0.0) + 1.0   # re-centre a stalled iterate in place
                 lam = np.ones(m)
                 rp_c = None
