@@ -38,6 +38,8 @@
 //                     step.  Inequality rows map three/four per lane; reductions (ratio test,
 //                     complementarity) are 16-lane DPP butterflies.
 #include "osc_internal.hpp"
+#include "osc_kin_model.hpp"
+#include "osc_mixed.h"
 
 using namespace osc;
 
@@ -499,6 +501,162 @@ bool warm_small(const osc_model* model, int32_t nenv, const double* warm, size_t
   return bytes >= need;
 }
 }  // namespace
+
+// ---- the mixed-robot tick (include/osc_mixed.h) ----
+namespace {
+
+bool on_kin_device(const osc_kin_model* kin) {
+  int cur = -1;
+  return hipGetDevice(&cur) == hipSuccess && cur == kin->device;
+}
+
+int check_tick_job(const osc_tick_job& j) {
+  if (!j.model || j.nenv < 0) return OSC_ERR_INVALID_ARGUMENT;
+  if (j.model->kid == K_NONE) return OSC_ERR_UNSUPPORTED_DIMS;
+  // wheel rows: their per-env directions are not part of the job, nor their kernels of the grid
+  if (j.model->kid == K_WALTER_WHEELS) return OSC_ERR_INVALID_ARGUMENT;
+  if (!on_model_device(j.model)) return OSC_ERR_INVALID_ARGUMENT;   // one device per call
+  if (j.kin != nullptr &&
+      (j.kin->host.nv != j.model->desc.nv || j.kin->host.nsite != j.model->desc.ns ||
+       j.kin->device != j.model->device))
+    return OSC_ERR_INVALID_ARGUMENT;
+  if (j.nenv == 0) return OSC_OK;
+  if (!j.workspace || !j.contact_mask || !j.T || !j.tau || misaligned16(j.workspace) ||
+      misaligned16(j.contact_mask) || misaligned16(j.T))
+    return OSC_ERR_INVALID_ARGUMENT;
+  size_t need = 0;
+  if (j.kin != nullptr) {
+    if (!j.qpos || !j.qvel) return OSC_ERR_INVALID_ARGUMENT;
+    need = osc_kin::QposWorkspace(j.model, j.kin->host, j.nenv).total;
+  } else {
+    if (!j.M || !j.C || !j.J || !j.b || misaligned16(j.M) || misaligned16(j.C) ||
+        misaligned16(j.J) || misaligned16(j.b))
+      return OSC_ERR_INVALID_ARGUMENT;
+    osc_workspace_bytes(j.model, j.nenv, &need);
+  }
+  if (j.workspace_bytes < need) return OSC_ERR_INVALID_ARGUMENT;
+  if (j.warm_state != nullptr &&
+      (misaligned16(j.warm_state) || !warm_small(j.model, j.nenv, j.warm_state, j.warm_state_bytes)))
+    return OSC_ERR_INVALID_ARGUMENT;
+  return OSC_OK;
+}
+
+// the job as the two-model grids take it: a joint-state job's M, C, J, b and reduced QPs are the
+// sections of its workspace (osc_qpos_workspace_bytes), as in osc_batch_solve_qpos
+PairTick pair_tick(const osc_tick_job& j) {
+  PairTick t{};
+  t.model = j.model;
+  t.nenv = j.nenv;
+  t.kin = j.kin;
+  t.qpos = j.qpos;
+  t.qvel = j.qvel;
+  if (j.kin != nullptr) {
+    const osc_kin::QposWorkspace L(j.model, j.kin->host, j.nenv);
+    char* base = static_cast<char*>(j.workspace);
+    t.M = reinterpret_cast<double*>(base + L.m);
+    t.C = reinterpret_cast<double*>(base + L.c);
+    t.J = reinterpret_cast<double*>(base + L.j);
+    t.b = reinterpret_cast<double*>(base + L.b);
+    t.ws = reinterpret_cast<double*>(base + L.ws);
+  } else {
+    t.M = const_cast<double*>(j.M);   // (read only: the kinematics writes a joint-state job's)
+    t.C = const_cast<double*>(j.C);
+    t.J = const_cast<double*>(j.J);
+    t.b = const_cast<double*>(j.b);
+    t.ws = static_cast<double*>(j.workspace);
+  }
+  t.T = j.T;
+  t.mask = j.contact_mask;
+  t.tau = j.tau;
+  t.x = j.x;
+  t.status = j.status;
+  t.iters = j.iters;
+  t.warm = j.warm_state;
+  return t;
+}
+
+// one job alone: the matching single-model entry
+int tick_solo(const osc_tick_job& j, void* stream) {
+  if (j.kin != nullptr)
+    return j.warm_state
+               ? osc_batch_solve_qpos_warm(j.model, j.kin, j.nenv, j.qpos, j.qvel, j.T,
+                                           j.contact_mask, j.tau, j.x, j.status, j.iters,
+                                           j.warm_state, j.warm_state_bytes, j.workspace,
+                                           j.workspace_bytes, stream)
+               : osc_batch_solve_qpos(j.model, j.kin, j.nenv, j.qpos, j.qvel, j.T, j.contact_mask,
+                                      j.tau, j.x, j.status, j.iters, j.workspace,
+                                      j.workspace_bytes, stream);
+  return j.warm_state
+             ? osc_batch_solve_warm(j.model, j.nenv, j.M, j.C, j.J, j.b, j.T, j.contact_mask, j.tau,
+                                    j.x, j.status, j.iters, j.warm_state, j.warm_state_bytes,
+                                    j.workspace, j.workspace_bytes, stream)
+             : osc_batch_solve(j.model, j.nenv, j.M, j.C, j.J, j.b, j.T, j.contact_mask, j.tau, j.x,
+                               j.status, j.iters, j.workspace, j.workspace_bytes, stream);
+}
+
+}  // namespace
+
+extern "C" int osc_batch_tick_multi(const osc_tick_job* jobs, int32_t njobs, void* stream) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return OSC_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < njobs; ++i) {   // every job checked before anything is launched
+    const int rc = check_tick_job(jobs[i]);
+    if (rc != OSC_OK) return rc;
+  }
+  // The two-model grids: osc_batch_solve_multi's rule, and both models with the refinement on
+  // (the grids' kernels fuse it; a model tuned without it runs its own pass sequence alone).
+  const auto kid_pair = [&](KernelId p, KernelId q) {
+    return jobs[0].model->kid == p && jobs[1].model->kid == q;
+  };
+  if (njobs == 2 && jobs[0].nenv > 0 && jobs[1].nenv > 0 &&
+      (kid_pair(K_WALTER, K_GO2) || kid_pair(K_GO2, K_WALTER)) &&
+      jobs[0].nenv <= jobs[0].model->small_batch_max &&
+      jobs[1].nenv <= jobs[1].model->small_batch_max && jobs[0].model->refine &&
+      jobs[1].model->refine) {
+    const bool a_walter = jobs[0].model->kid == K_WALTER;
+    const osc_tick_job& w = a_walter ? jobs[0] : jobs[1];   // slower per wavefront: first
+    const osc_tick_job& g = a_walter ? jobs[1] : jobs[0];
+    const PairTick tw = pair_tick(w), tg = pair_tick(g);
+    // a joint-state job next to a QP job: its kinematics alone, then the grids
+    for (const PairTick* t : {&tw, &tg})
+      if (t->kin != nullptr && (tw.kin == nullptr || tg.kin == nullptr)) {
+        const int rc = osc_batch_kinematics(t->kin, t->nenv, t->qpos, t->qvel, t->M, t->C, t->J,
+                                            t->b, nullptr, stream);
+        if (rc != OSC_OK) return rc;
+      }
+    launch_pair_tick_walter_go2(tw, tg, static_cast<hipStream_t>(stream));
+    return hipGetLastError() == hipSuccess ? OSC_OK : OSC_ERR_DEVICE;
+  }
+  for (int i = 0; i < njobs; ++i) {
+    const int rc = tick_solo(jobs[i], stream);
+    if (rc != OSC_OK) return rc;
+  }
+  return OSC_OK;
+}
+
+extern "C" int osc_batch_kinematics_pair(const osc_kin_model* kin_a, int32_t nenv_a,
+                                         const double* qpos_a, const double* qvel_a, double* M_a,
+                                         double* C_a, double* J_a, double* b_a,
+                                         const osc_kin_model* kin_b, int32_t nenv_b,
+                                         const double* qpos_b, const double* qvel_b, double* M_b,
+                                         double* C_b, double* J_b, double* b_b, void* stream) {
+  if (!kin_a || !kin_b || nenv_a < 0 || nenv_b < 0) return OSC_ERR_INVALID_ARGUMENT;
+  if (!on_kin_device(kin_a) || !on_kin_device(kin_b)) return OSC_ERR_INVALID_ARGUMENT;
+  if ((nenv_a > 0 && (!qpos_a || !qvel_a || !M_a || !C_a || !J_a || !b_a)) ||
+      (nenv_b > 0 && (!qpos_b || !qvel_b || !M_b || !C_b || !J_b || !b_b)))
+    return OSC_ERR_INVALID_ARGUMENT;
+  if (nenv_a == 0 || nenv_b == 0) {   // one model's envs only: its own grid
+    if (nenv_a > 0)
+      return osc_batch_kinematics(kin_a, nenv_a, qpos_a, qvel_a, M_a, C_a, J_a, b_a, nullptr, stream);
+    return osc_batch_kinematics(kin_b, nenv_b, qpos_b, qvel_b, M_b, C_b, J_b, b_b, nullptr, stream);
+  }
+  PairTick a{}, b{};
+  a.kin = kin_a; a.nenv = nenv_a; a.qpos = qpos_a; a.qvel = qvel_a;
+  a.M = M_a; a.C = C_a; a.J = J_a; a.b = b_a;
+  b.kin = kin_b; b.nenv = nenv_b; b.qpos = qpos_b; b.qvel = qvel_b;
+  b.M = M_b; b.C = C_b; b.J = J_b; b.b = b_b;
+  launch_kin_pair(a, b, static_cast<hipStream_t>(stream));
+  return hipGetLastError() == hipSuccess ? OSC_OK : OSC_ERR_DEVICE;
+}
 
 extern "C" int osc_batch_solve_warm(const osc_model* model, int32_t nenv, const double* M,
                                     const double* C, const double* J, const double* b,

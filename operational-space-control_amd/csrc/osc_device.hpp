@@ -13,7 +13,7 @@
 //                                                         osc_ipm_launch.hpp (kernels, launch_ipm)
 //   osc_dual.hip        kernel 3  osc_dual_kernel        (dual solution, optional)
 //   osc_gi.hip          kernel 4  osc_gi_kernel          (wheel-row active-set fallback)
-//   osc_multi.hip       the two-model grids of osc_batch_solve_multi
+//   osc_multi.hip       the two-model grids of osc_batch_solve_multi / osc_batch_tick_multi
 //   osc_api.hip         the C-ABI (include/osc_batch.h): models, tuning, launch sequencing
 #pragma once
 #include <hip/hip_runtime.h>
@@ -617,6 +617,7 @@ struct PairArgs {
   double* ws;
   double *tau, *x;
   int32_t *status, *iters;
+  double* warm = nullptr;   // warm state (the warm pair kernels; a NULL job runs cold beside it)
 };
 
 using Go2 = Dims<18, 12, 4, 5>;   // unitree_go2: nv 18, nu 12, 4 feet, 5 sites

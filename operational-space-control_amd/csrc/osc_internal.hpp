@@ -4,6 +4,7 @@
 // from the translation unit that holds its device code: no relocatable device code here).
 #pragma once
 #include "osc_device.hpp"
+#include "osc_kinematics.h"
 #include "osc_qpos.hpp"
 
 struct osc_model {
@@ -44,6 +45,26 @@ template <class D> void launch_dual(const LaunchArgs& a);    // osc_dual.hip
 template <class D> void launch_gi(const LaunchArgs& a);      // osc_gi.hip
 // osc_multi.hip: WaLTER's job and Go2's job in one assembly grid and one interior-point grid
 void launch_pair_walter_go2(const osc_batch_job& w, const osc_batch_job& g, hipStream_t s);
+
+// One model's job of a two-model tick (osc_batch_tick_multi): QP inputs M, C, J, b, or -- kin set
+// -- joint states, with M, C, J, b the arrays the kinematics writes (the job's workspace).
+struct PairTick {
+  const osc_model* model;
+  int32_t nenv;
+  const osc_kin_model* kin;
+  const double *qpos, *qvel;
+  double *M, *C, *J, *b;
+  const double *T, *mask;
+  double *tau, *x;
+  int32_t *status, *iters;
+  double* ws;            // the reduced QPs (osc_workspace_bytes)
+  double* warm;          // nullable: the job runs cold
+};
+// osc_multi.hip: the tick's grids, WaLTER's wavefronts first -- the kinematics of both models when
+// both jobs carry joint states (else the caller ran a lone one's), the assembly, the interior point
+void launch_pair_tick_walter_go2(const PairTick& w, const PairTick& g, hipStream_t s);
+// the kinematics grid alone (both jobs' kin, qpos, qvel, M, C, J, b and nenv > 0)
+void launch_kin_pair(const PairTick& a, const PairTick& b, hipStream_t s);
 
 extern template void launch_setup<Go2>(const LaunchArgs&);
 extern template void launch_setup<Walter>(const LaunchArgs&);

@@ -59,139 +59,17 @@ namespace {
 
 using namespace osc_kin;
 
-constexpr int kWave = 64;
-constexpr int kRow = 16;
-constexpr int kEnvPerWave = kWave / kRow;
-// Diagnostic builds only (tools/kin_ablate.sh): -DOSC_KIN_STOP=k ends the kernel before stage k.
-#ifdef OSC_KIN_STOP
-#define KIN_STOP(k) do { if ((k) == OSC_KIN_STOP) return; } while (0)
-#else
-#define KIN_STOP(k) do {} while (0)
-#endif
+constexpr int kWave = kKinWave;
+constexpr int kEnvPerWave = kKinEnvPerWave;
 
+// One model's batch: the body is kin_block (osc_kin_device.hpp), shared with the two-model grid.
 __global__ __launch_bounds__(kWave) void osc_kinematics_kernel(
     const KinDev* __restrict__ Kg, int nenv, const double* __restrict__ qpos,
     const double* __restrict__ qvel, double* __restrict__ gM, double* __restrict__ gC,
     double* __restrict__ gJ, double* __restrict__ gb, double* __restrict__ gx) {
   extern __shared__ __attribute__((aligned(16))) double kin_sm[];
-  // The model tables are indexed per lane (body / dof / site differ across lanes), so they are
-  // staged into LDS once per workgroup: ~64-cycle LDS reads instead of dependent L2 round trips
-  // in every output-element iteration.
   __shared__ __attribute__((aligned(16))) KinDev sK;
-  {
-    static_assert(sizeof(KinDev) % 16 == 0, "16-byte staging of the model tables");
-    const uint4* src = reinterpret_cast<const uint4*>(Kg);
-    uint4* dst = reinterpret_cast<uint4*>(&sK);
-    for (int i = threadIdx.x; i < static_cast<int>(sizeof(KinDev) / 16); i += kWave) dst[i] = src[i];
-  }
-  wave_sync();
-  const KinDev* K = &sK;
-  const int lane = threadIdx.x;
-  const int row = lane / kRow, l = lane % kRow;
-  const int env_raw = blockIdx.x * kEnvPerWave + row;
-  const bool valid = env_raw < nenv;
-  const int env = valid ? env_raw : nenv - 1;   // tail rows recompute the last env, store nothing
-  const int nq = Kg->nq, nv = Kg->nv, nb = Kg->nbody, ns = Kg->nsite;
-  const EnvLayout lay(nq, nv, nb, ns);
-  double* E = kin_sm + row * lay.size;
-
-  // ---- stage 0: qpos | qvel -> LDS --------------------------------------------------------
-  for (int i = l; i < nq; i += kRow) E[lay.q + i] = qpos[static_cast<size_t>(env) * nq + i];
-  for (int i = l; i < nv; i += kRow) E[lay.q + nq + i] = qvel[static_cast<size_t>(env) * nv + i];
-  wave_sync();
-
-  KIN_STOP(0);
-  // ---- stage 1: forward pass, level by level (lane = body) --------------------------------
-  kin_forward(K, E, lay, l);
-
-  KIN_STOP(1);
-  // ---- stage 2: backward pass: subtree composite inertia and force ------------------------
-  kin_backward(K, E, lay, l);
-
-  KIN_STOP(2);
-  // ---- stage 3: dofs (lane = dof): motion subspace S, F = Ic S, C = S . f -----------------
-  for (int d = l; d < nv; d += kRow) {
-    const double cd = kin_dof(K, E, lay, d);
-    if (valid) gC[static_cast<size_t>(env) * nv + d] = cd;
-  }
-
-  KIN_STOP(3);
-  // ---- stage 4: sites (lane = site): world position, J-dot qvel ---------------------------
-  for (int k = l; k < ns; k += kRow) {
-    double bp[3], br[3];
-    kin_site(K, E, lay, k, bp, br);
-    if (valid) {
-      double* bo = gb + static_cast<size_t>(env) * 6 * ns;
-      for (int i = 0; i < 3; ++i) {
-        bo[3 * k + i] = bp[i];
-        bo[3 * ns + 3 * k + i] = br[i];
-      }
-      if (gx) {
-        const double* xs = E + lay.site + 3 * k;
-        for (int i = 0; i < 3; ++i) gx[(static_cast<size_t>(env) * ns + k) * 3 + i] = xs[i];
-      }
-    }
-  }
-  wave_sync();
-
-  KIN_STOP(4);
-  // ---- stage 5: M (lane = columns l, l + 16; uniform loop over rows) -----------------------
-  // M_ij = S_lo . (Ic S_hi) for related dofs (lo = min(i, j)); lane j keeps S_j, F_j in
-  // registers, row i's S_i, F_i are row-broadcast LDS reads, relations come from per-dof masks
-  // (scalar loads).  Every store writes 16 consecutive doubles of one row.
-  const int c0 = l, c1 = l + kRow;
-  const bool v0 = c0 < nv, v1 = c1 < nv;
-  double S0[6], F0[6], S1[6], F1[6];
-  {
-    const double* D0 = E + lay.dof + kDofStride * (v0 ? c0 : 0);
-    const double* D1 = E + lay.dof + kDofStride * (v1 ? c1 : 0);
-    for (int t = 0; t < 6; ++t) {
-      S0[t] = D0[t]; F0[t] = D0[6 + t];
-      S1[t] = D1[t]; F1[t] = D1[6 + t];
-    }
-  }
-  {
-    double* Mo = gM + static_cast<size_t>(env) * nv * nv;
-    for (int i = 0; i < nv; ++i) {
-      const uint32_t rel = K->dof_relmask[i];
-      const double arm = K->dof_arm[i];
-      const double* Di = E + lay.dof + kDofStride * i;
-      double Si[6], Fi[6];
-      for (int t = 0; t < 6; ++t) {
-        Si[t] = Di[t];
-        Fi[t] = Di[6 + t];
-      }
-      const double m0 = kin_m_entry(rel, arm, i, c0, Si, Fi, S0, F0);
-      const double m1 = kin_m_entry(rel, arm, i, c1, Si, Fi, S1, F1);
-      if (valid && v0) Mo[i * nv + c0] = m0;
-      if (valid && v1) Mo[i * nv + c1] = m1;
-    }
-  }
-
-  KIN_STOP(5);
-  // ---- stage 6: J (lane = columns l, l + 16; uniform loop over sites) ---------------------
-  // column c of site k (c an ancestor dof of the site's body): Jr = S_c.w, Jp = S_c.v +
-  // S_c.w x x_k; rows 3k..3k+2 (Jp) and 3ns+3k.. (Jr).
-  {
-    double* Jo = gJ + static_cast<size_t>(env) * 6 * ns * nv;
-    for (int k = 0; k < ns; ++k) {
-      const uint32_t rel = K->site_dofmask[k];
-      const double* xs = E + lay.site + 3 * k;
-      const double xk[3] = {xs[0], xs[1], xs[2]};
-      auto col = [&](int c, bool vc, const double* S) {
-        double jp[3], jr[3];
-        kin_j_col(vc && ((rel >> c) & 1u), S, xk, jp, jr);
-        for (int t = 0; t < 3; ++t) {
-          if (valid && vc) {
-            Jo[(3 * k + t) * nv + c] = jp[t];
-            Jo[(3 * ns + 3 * k + t) * nv + c] = jr[t];
-          }
-        }
-      };
-      col(c0, v0, S0);
-      col(c1, v1, S1);
-    }
-  }
+  kin_block(Kg, &sK, kin_sm, static_cast<int>(blockIdx.x), nenv, qpos, qvel, gM, gC, gJ, gb, gx);
 }
 
 constexpr int kPackBlock = 256;
@@ -612,23 +490,6 @@ extern "C" int osc_state_to_qpos(int32_t nenv, int32_t nu, const double* body_ro
 }
 
 namespace {
-
-size_t align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
-
-struct QposWorkspace {   // [M | C | J | b | reduced-QP workspace], each section 256-B aligned
-  size_t m, c, j, b, ws, ws_bytes, total;
-  QposWorkspace(const osc_model* model, const KinDev& k, int32_t nenv) {
-    const size_t n = static_cast<size_t>(nenv);
-    m = 0;
-    c = m + align256(sizeof(double) * n * k.nv * k.nv);
-    j = c + align256(sizeof(double) * n * k.nv);
-    b = j + align256(sizeof(double) * n * 6 * k.nsite * k.nv);
-    ws = b + align256(sizeof(double) * n * 6 * k.nsite);
-    ws_bytes = 0;
-    osc_workspace_bytes(model, nenv, &ws_bytes);
-    total = ws + align256(ws_bytes);
-  }
-};
 
 int check_pair(const osc_model* model, const osc_kin_model* kin) {
   if (!model || !kin) return OSC_ERR_INVALID_ARGUMENT;

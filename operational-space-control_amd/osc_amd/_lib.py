@@ -45,6 +45,12 @@ ROLLOUT_SYMBOLS = ("osc_batch_integrate", "osc_rollout_workspace_bytes", "osc_ba
 ROLLOUT_WARM = 1
 ROLLOUT_TARGETS_HELD, ROLLOUT_TARGETS_PD_BASE = 0, 1
 
+# include/osc_mixed.h (the mixed-robot tick), apart for the same reason; tests/test_mixed_abi.py
+# pins this list to that header's declarations.
+MIXED_SYMBOLS = ("osc_batch_tick_multi", "osc_batch_kinematics_pair",
+                 "osc_host_feed_create_multi", "osc_host_feed_inputs_part",
+                 "osc_host_feed_wait_part")
+
 OSC_KIN_MAX_BODIES = 16
 OSC_KIN_MAX_DOFS = 32
 OSC_KIN_MAX_SITES = 32
@@ -100,6 +106,20 @@ class OscBatchJob(ctypes.Structure):
         [(n, ctypes.c_void_p) for n in ("M", "C", "J", "b", "T", "contact_mask", "tau", "x",
                                          "status", "iters", "workspace")] + \
         [("workspace_bytes", ctypes.c_size_t), ("wheel_dir", ctypes.c_void_p)]
+
+
+class OscTickJob(ctypes.Structure):
+    """osc_tick_job (include/osc_mixed.h): one model's tick inside osc_batch_tick_multi."""
+    _fields_ = [("model", ctypes.c_void_p), ("kin", ctypes.c_void_p), ("nenv", ctypes.c_int32)] + \
+        [(n, ctypes.c_void_p) for n in ("M", "C", "J", "b", "qpos", "qvel", "T", "contact_mask",
+                                         "tau", "x", "status", "iters", "warm_state")] + \
+        [("warm_state_bytes", ctypes.c_size_t), ("workspace", ctypes.c_void_p),
+         ("workspace_bytes", ctypes.c_size_t)]
+
+
+class OscFeedPart(ctypes.Structure):
+    """osc_feed_part (include/osc_mixed.h): one model's share of a two-model host feed."""
+    _fields_ = [("model", ctypes.c_void_p), ("kin", ctypes.c_void_p), ("nenv", ctypes.c_int32)]
 
 
 _B, _S = OSC_KIN_MAX_BODIES, OSC_KIN_MAX_SITES
@@ -282,6 +302,17 @@ def lib() -> ctypes.CDLL:
     L.osc_host_feed_wait.restype = ctypes.c_int
     L.osc_host_feed_timing.argtypes = [vp, i32, ctypes.POINTER(OscFeedTiming)]
     L.osc_host_feed_timing.restype = ctypes.c_int
+    L.osc_batch_tick_multi.argtypes = [ctypes.POINTER(OscTickJob), i32, vp]
+    L.osc_batch_tick_multi.restype = ctypes.c_int
+    L.osc_batch_kinematics_pair.argtypes = ([vp, i32] + [vp] * 6) * 2 + [vp]
+    L.osc_batch_kinematics_pair.restype = ctypes.c_int
+    L.osc_host_feed_create_multi.argtypes = [ctypes.POINTER(OscFeedPart), i32, i32,
+                                             ctypes.c_uint32, i32, ctypes.POINTER(vp)]
+    L.osc_host_feed_create_multi.restype = ctypes.c_int
+    L.osc_host_feed_inputs_part.argtypes = [vp, i32, i32, ctypes.POINTER(OscFeedInputs)]
+    L.osc_host_feed_inputs_part.restype = ctypes.c_int
+    L.osc_host_feed_wait_part.argtypes = [vp, i32, i32, ctypes.POINTER(OscFeedOutputs)]
+    L.osc_host_feed_wait_part.restype = ctypes.c_int
     _lib = L
     return L
 

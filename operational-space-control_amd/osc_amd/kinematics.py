@@ -340,3 +340,18 @@ def random_states(tree: dict, nenv: int, seed: int, base_pos_zero: bool = True,
             qpos[:, qa] = rng.uniform(-0.3 * joint_range, 0.3 * joint_range, size=nenv)
         qa += nqj[t]
     return qpos, qvel
+
+
+def kinematics_pair_into(kin_a: KinematicsBatch, out_a: KinOutputs, qpos_a, qvel_a,
+                         kin_b: KinematicsBatch, out_b: KinOutputs, qpos_b, qvel_b,
+                         stream=None) -> None:
+    """osc_batch_kinematics_pair (include/osc_mixed.h): two models' kinematics in one grid, each
+    model's M, C, J, b bitwise compute_into's."""
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    side = lambda k, o, qp, qv: [k._h, o.M.shape[0], ptr(qp), ptr(qv), ptr(o.M), ptr(o.C),
+                                 ptr(o.J), ptr(o.b)]
+    rc = _lib.lib().osc_batch_kinematics_pair(
+        *side(kin_a, out_a, qpos_a, qvel_a), *side(kin_b, out_b, qpos_b, qvel_b),
+        ctypes.c_void_p(KinematicsBatch._stream(stream, kin_a.device)))
+    if rc != 0:
+        raise _lib.OSCError("osc_batch_kinematics_pair", rc)

@@ -283,3 +283,55 @@ def solve_multi_into(jobs, stream=None) -> None:
     rc = _lib.lib().osc_batch_solve_multi(arr, len(jobs), ctypes.c_void_p(s))
     if rc != 0:
         raise _lib.OSCError("osc_batch_solve_multi", rc)
+
+
+@dataclasses.dataclass
+class TickJob:
+    """One model's tick inside tick_multi_into (osc_tick_job, include/osc_mixed.h).
+    inputs: (M, C, J, b, T, mask) device tensors, or with `kin` (a KinematicsBatch of the same
+    robot) (qpos, qvel, T, mask).  warm: the job's warm-state tensor (solver.alloc_warm_state),
+    None = cold.  workspace: with `kin` a tensor of kin.workspace_bytes(solver, nenv); without,
+    out.workspace is used."""
+    solver: OSCBatchSolver
+    out: SolveResult
+    inputs: tuple
+    kin: object | None = None
+    warm: torch.Tensor | None = None
+    workspace: torch.Tensor | None = None
+
+
+def tick_jobs_array(jobs):
+    """The osc_tick_job array of a list of TickJob (device pointers only: keep `jobs` alive)."""
+    arr = (_lib.OscTickJob * max(len(jobs), 1))()
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    for j, job in zip(arr, jobs):
+        out = job.out
+        j.model = job.solver._h.value
+        j.nenv = out.tau.shape[0]
+        if job.kin is not None:
+            j.kin = job.kin._h.value
+            qpos, qvel, T, mask = job.inputs
+            j.qpos, j.qvel = ptr(qpos), ptr(qvel)
+        else:
+            M, C, J, b, T, mask = job.inputs
+            j.M, j.C, j.J, j.b = ptr(M), ptr(C), ptr(J), ptr(b)
+        j.T, j.contact_mask = ptr(T), ptr(mask)
+        j.tau, j.x, j.status, j.iters = ptr(out.tau), ptr(out.x), ptr(out.status), ptr(out.iters)
+        if job.warm is not None:
+            j.warm_state, j.warm_state_bytes = ptr(job.warm), job.warm.numel() * 8
+        ws = job.workspace if job.workspace is not None else out.workspace
+        if ws is not None:
+            j.workspace, j.workspace_bytes = ptr(ws), ws.numel() * ws.element_size()
+    return arr
+
+
+def tick_multi_into(jobs, stream=None) -> None:
+    """osc_batch_tick_multi: several models' ticks in one call on one stream -- the mixed-robot
+    tick with warm starts and joint-state inputs per job (BASELINE configs[4]).  `jobs` is a list
+    of TickJob; each job's results are bitwise those of its single-model call."""
+    arr = tick_jobs_array(jobs)
+    dev = jobs[-1].solver.device if jobs else None
+    s = (torch.cuda.current_stream(dev) if stream is None else stream).cuda_stream
+    rc = _lib.lib().osc_batch_tick_multi(arr, len(jobs), ctypes.c_void_p(s))
+    if rc != 0:
+        raise _lib.OSCError("osc_batch_tick_multi", rc)
