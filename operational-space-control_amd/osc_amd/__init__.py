@@ -13,4 +13,7 @@ def __getattr__(name):
     if name in ("OSCBatchSolver", "SolveResult"):
         from . import solver
         return getattr(solver, name)
+    if name == "solve_differentiable":
+        from . import autograd
+        return autograd.solve_differentiable
     raise AttributeError(name)

@@ -43,6 +43,8 @@ EXPORTED_SYMBOLS = ("osc_desc_from_yaml", "osc_model_create", "osc_model_create_
 # declarations of the four headers it reads; tests/test_rollout_ref.py pins this list likewise.
 ROLLOUT_SYMBOLS = ("osc_batch_integrate", "osc_rollout_workspace_bytes", "osc_batch_rollout")
 ROLLOUT_WARM = 1
+# include/osc_backward.h, pinned by tests/test_backward_ref.py
+BACKWARD_SYMBOLS = ("osc_batch_solve_backward",)
 ROLLOUT_TARGETS_HELD, ROLLOUT_TARGETS_PD_BASE = 0, 1
 
 # include/osc_mixed.h (the mixed-robot tick), apart for the same reason; tests/test_mixed_abi.py
@@ -290,6 +292,8 @@ def lib() -> ctypes.CDLL:
     L.osc_rollout_workspace_bytes.restype = ctypes.c_int
     L.osc_batch_rollout.argtypes = [vp, vp, i32, ctypes.POINTER(OscRolloutArgs), vp]
     L.osc_batch_rollout.restype = ctypes.c_int
+    L.osc_batch_solve_backward.argtypes = [vp, i32] + [vp] * 8 + [ctypes.c_size_t, vp]
+    L.osc_batch_solve_backward.restype = ctypes.c_int
     L.osc_host_feed_create.argtypes = [vp, vp, i32, i32, ctypes.c_uint32, i32, ctypes.POINTER(vp)]
     L.osc_host_feed_create.restype = ctypes.c_int
     L.osc_host_feed_destroy.argtypes = [vp]

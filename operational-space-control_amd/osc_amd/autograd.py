@@ -1,0 +1,63 @@
+"""torch.autograd through the batched OSC solve: gradients of (tau, x) with respect to the task
+targets T and the task bias b (include/osc_backward.h).
+
+    tau, x, status = solve_differentiable(solver, M, C, J, b, T, mask)
+    loss(tau, x).backward()        # T.grad, b.grad
+
+The forward is OSCBatchSolver.solve_into with the design vector and the duals; the backward is one
+launch of osc_batch_solve_backward on the forward's workspace.  Gradients flow to T and b ONLY:
+M, C, J and mask get None (the derivative with respect to them is not implemented, and a None is
+not a zero), so M, C or J with requires_grad raise instead of silently training nothing.
+"""
+from __future__ import annotations
+
+import torch
+
+from .solver import OSCBatchSolver
+
+
+class _OSCSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, M, C, J, b, T, mask):
+        nenv = int(M.shape[0])
+        out = solver.alloc_outputs(nenv, want_x=True, want_y=True)
+        with torch.cuda.device(solver.device):
+            solver.solve_into(out, M, C, J, b, T, mask)
+        ctx.solver, ctx.out = solver, out
+        ctx.save_for_backward(J, mask)
+        ctx.mark_non_differentiable(out.status)
+        return out.x, out.status
+
+    @staticmethod
+    def backward(ctx, grad_x, _grad_status):
+        solver, out = ctx.solver, ctx.out
+        J, mask = ctx.saved_tensors
+        d = solver.dims
+        nenv = out.tau.shape[0]
+        need_b, need_T = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        if grad_x is None or not (need_b or need_T):
+            return (None,) * 7
+        grad_x = grad_x.to(dtype=torch.float64).contiguous()
+        opts = dict(dtype=torch.float64, device=solver.device)
+        grad_T = torch.empty((nenv, d["ns"], 6), **opts) if need_T else None
+        grad_b = torch.empty((nenv, d["s"]), **opts) if need_b else None
+        with torch.cuda.device(solver.device):
+            solver.backward_into(out, J, mask, grad_x, grad_T, grad_b)
+        return None, None, None, None, grad_b, grad_T, None
+
+
+def solve_differentiable(solver: OSCBatchSolver, M, C, J, b, T, mask):
+    """(tau, x, status) of the batch, differentiable with respect to T and b.
+
+    Inputs are float64 tensors on the solver's device in the C-ABI's layout (solver.prepare).  tau
+    is the slice x[:, nv:nv + nu], so a loss on either reaches the same backward.  Gradients flow
+    to T and b only; M, C, J and mask get None, and M, C or J with requires_grad raise ValueError.
+    An env whose status is not 0 contributes zero gradients.  The model must have no wheel rows."""
+    for name, t in (("M", M), ("C", C), ("J", J)):
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise ValueError(f"solve_differentiable: no gradient with respect to {name} "
+                             "(only T and b are differentiated)")
+    M, C, J, b, T, mask = solver.prepare(M, C, J, b, T, mask)
+    x, status = _OSCSolve.apply(solver, M, C, J, b, T, mask)
+    d = solver.dims
+    return x[:, d["nv"]:d["nv"] + d["nu"]], x, status

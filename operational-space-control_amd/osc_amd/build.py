@@ -28,8 +28,8 @@ ARCH = os.environ.get("OSC_OFFLOAD_ARCH", "gfx950")
 # kernel units (csrc/osc_device.hpp lists what each holds) + host units
 SOURCES = ["osc_ipm_go2.hip", "osc_ipm_walter.hip", "osc_ipm_wheels.hip", "osc_multi.hip",
            "osc_setup.hip", "osc_gi.hip", "osc_dual.hip", "osc_kinematics.hip",
-           "osc_producers.hip", "osc_rollout.hip", "osc_api.hip", "osc_model.cpp", "osc_mjcf.cpp",
-           "osc_host_feed.cpp"]
+           "osc_producers.hip", "osc_rollout.hip", "osc_backward.hip", "osc_api.hip",
+           "osc_model.cpp", "osc_mjcf.cpp", "osc_host_feed.cpp"]
 # every header of csrc/ (the up-to-date check's dependency list: a new header is picked up by name)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp"))
 # Per-unit compiler flags (variant builds may pass their own map to build()).  The interior-point
@@ -65,7 +65,8 @@ def build(verbose: bool = False, force: bool = False, out: str | None = None,
     deps = srcs + [os.path.join(CSRC, h) for h in HEADERS] + \
         [os.path.join(REPO, "include", h) for h in ("osc_batch.h", "osc_producers.h",
                                                      "osc_kinematics.h", "osc_host_feed.h",
-                                                     "osc_rollout.h", "osc_mixed.h")] + [__file__]
+                                                     "osc_rollout.h", "osc_mixed.h",
+                                                     "osc_backward.h")] + [__file__]
     variant = out != OUT
     if not force and os.path.exists(out):
         t_out = os.path.getmtime(out)

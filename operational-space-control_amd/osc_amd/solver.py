@@ -185,6 +185,26 @@ class OSCBatchSolver:
             raise _lib.OSCError("osc_batch_solve_assembled", rc)
         return out
 
+    def backward_into(self, out: SolveResult, J, mask, grad_x, grad_T, grad_b,
+                      stream=None) -> None:
+        """Launch only: osc_batch_solve_backward (include/osc_backward.h).  dL/dT into grad_T
+        (nenv, ns, 6) and dL/db into grad_b (nenv, 6 ns), either None, from grad_x = dL/dx
+        (nenv, nv + nu + 3 nc) over the whole design vector.  `out` is the SolveResult of the
+        forward solve_into with x and y on the same J and mask; its workspace must not have been
+        reused since.  An env whose status is not 0 gets zero gradients."""
+        if out.y is None or out.workspace is None:
+            raise ValueError("backward_into needs the forward solve's duals and workspace "
+                             "(alloc_outputs(want_x=True, want_y=True))")
+        nenv = out.tau.shape[0]
+        s = (torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = _lib.lib().osc_batch_solve_backward(
+            self._h, nenv, ptr(J), ptr(mask), ptr(out.y), ptr(out.status), ptr(grad_x),
+            ptr(grad_T), ptr(grad_b), ptr(out.workspace),
+            ctypes.c_size_t(out.workspace.numel() * 8), ctypes.c_void_p(s))
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_solve_backward", rc)
+
     def alloc_warm_state(self, nenv: int) -> torch.Tensor:
         """Zero-filled warm state (osc_warm_state_bytes): every env starts cold on its first tick."""
         nb = ctypes.c_size_t()
