@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = ("osc_desc_from_yaml", "osc_model_create", "osc_model_create_
 ROLLOUT_SYMBOLS = ("osc_batch_integrate", "osc_rollout_workspace_bytes", "osc_batch_rollout")
 ROLLOUT_WARM = 1
 # include/osc_backward.h, pinned by tests/test_backward_ref.py
-BACKWARD_SYMBOLS = ("osc_batch_solve_backward",)
+BACKWARD_SYMBOLS = ("osc_batch_solve_backward", "osc_batch_solve_backward_data")
 ROLLOUT_TARGETS_HELD, ROLLOUT_TARGETS_PD_BASE = 0, 1
 
 # include/osc_mixed.h (the mixed-robot tick), apart for the same reason; tests/test_mixed_abi.py
@@ -294,6 +294,8 @@ def lib() -> ctypes.CDLL:
     L.osc_batch_rollout.restype = ctypes.c_int
     L.osc_batch_solve_backward.argtypes = [vp, i32] + [vp] * 8 + [ctypes.c_size_t, vp]
     L.osc_batch_solve_backward.restype = ctypes.c_int
+    L.osc_batch_solve_backward_data.argtypes = [vp, i32] + [vp] * 16 + [ctypes.c_size_t, vp]
+    L.osc_batch_solve_backward_data.restype = ctypes.c_int
     L.osc_host_feed_create.argtypes = [vp, vp, i32, i32, ctypes.c_uint32, i32, ctypes.POINTER(vp)]
     L.osc_host_feed_create.restype = ctypes.c_int
     L.osc_host_feed_destroy.argtypes = [vp]

@@ -1,13 +1,19 @@
 """torch.autograd through the batched OSC solve: gradients of (tau, x) with respect to the task
-targets T and the task bias b (include/osc_backward.h).
+targets T and the task bias b and, with data_grads=True, the dynamics inputs M, C and J
+(include/osc_backward.h).
 
     tau, x, status = solve_differentiable(solver, M, C, J, b, T, mask)
     loss(tau, x).backward()        # T.grad, b.grad
 
+    tau, x, status = solve_differentiable(solver, M, C, J, b, T, mask, data_grads=True)
+    loss(tau, x).backward()        # M.grad, C.grad, J.grad as well
+
 The forward is OSCBatchSolver.solve_into with the design vector and the duals; the backward is one
-launch of osc_batch_solve_backward on the forward's workspace.  Gradients flow to T and b ONLY:
-M, C, J and mask get None (the derivative with respect to them is not implemented, and a None is
-not a zero), so M, C or J with requires_grad raise instead of silently training nothing.
+launch on the forward's workspace: osc_batch_solve_backward, or osc_batch_solve_backward_data
+with data_grads=True, filling only the gradients autograd asks for.  By default gradients flow to
+T and b ONLY: M, C, J and mask get None (a None is not a zero), so M, C or J with requires_grad
+raise instead of silently training nothing.  The mask never gets a gradient; the task weights are
+model constants, not tensors (their gradient: OSCBatchSolver.backward_data_into's grad_wrow).
 """
 from __future__ import annotations
 
@@ -46,18 +52,57 @@ class _OSCSolve(torch.autograd.Function):
         return None, None, None, None, grad_b, grad_T, None
 
 
-def solve_differentiable(solver: OSCBatchSolver, M, C, J, b, T, mask):
-    """(tau, x, status) of the batch, differentiable with respect to T and b.
+class _OSCSolveData(torch.autograd.Function):
+    """As _OSCSolve, differentiable with respect to M, C and J as well."""
+
+    @staticmethod
+    def forward(ctx, solver, M, C, J, b, T, mask):
+        nenv = int(M.shape[0])
+        out = solver.alloc_outputs(nenv, want_x=True, want_y=True)
+        with torch.cuda.device(solver.device):
+            solver.solve_into(out, M, C, J, b, T, mask)
+        ctx.solver, ctx.out = solver, out
+        ctx.save_for_backward(M, J, b, T, mask)
+        ctx.mark_non_differentiable(out.status)
+        return out.x, out.status
+
+    @staticmethod
+    def backward(ctx, grad_x, _grad_status):
+        solver, out = ctx.solver, ctx.out
+        M, J, b, T, mask = ctx.saved_tensors
+        d = solver.dims
+        nenv = out.tau.shape[0]
+        need = dict(zip(("M", "C", "J", "b", "T"), ctx.needs_input_grad[1:6]))
+        if grad_x is None or not any(need.values()):
+            return (None,) * 7
+        grad_x = grad_x.to(dtype=torch.float64).contiguous()
+        shape = dict(M=(nenv, d["nv"], d["nv"]), C=(nenv, d["nv"]), J=(nenv, d["s"], d["nv"]),
+                     b=(nenv, d["s"]), T=(nenv, d["ns"], 6))
+        g = {k: (torch.empty(shape[k], dtype=torch.float64, device=solver.device) if need[k]
+                 else None) for k in shape}
+        with torch.cuda.device(solver.device):
+            solver.backward_data_into(out, M, J, b, T, mask, grad_x, grad_M=g["M"], grad_C=g["C"],
+                                      grad_J=g["J"], grad_T=g["T"], grad_b=g["b"])
+        return None, g["M"], g["C"], g["J"], g["b"], g["T"], None
+
+
+def solve_differentiable(solver: OSCBatchSolver, M, C, J, b, T, mask, data_grads: bool = False):
+    """(tau, x, status) of the batch, differentiable with respect to T and b, and with
+    data_grads=True with respect to M, C and J as well.
 
     Inputs are float64 tensors on the solver's device in the C-ABI's layout (solver.prepare).  tau
-    is the slice x[:, nv:nv + nu], so a loss on either reaches the same backward.  Gradients flow
-    to T and b only; M, C, J and mask get None, and M, C or J with requires_grad raise ValueError.
-    An env whose status is not 0 contributes zero gradients.  The model must have no wheel rows."""
-    for name, t in (("M", M), ("C", C), ("J", J)):
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise ValueError(f"solve_differentiable: no gradient with respect to {name} "
-                             "(only T and b are differentiated)")
+    is the slice x[:, nv:nv + nu], so a loss on either reaches the same backward.  Without
+    data_grads gradients flow to T and b only; M, C, J and mask get None, and M, C or J with
+    requires_grad raise ValueError.  M.grad treats all nv^2 entries of M as independent (it is not
+    symmetrised).  An env whose status is not 0 contributes zero gradients.  The model must have
+    no wheel rows."""
+    if not data_grads:
+        for name, t in (("M", M), ("C", C), ("J", J)):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise ValueError(f"solve_differentiable: no gradient with respect to {name} "
+                                 "(only T and b are differentiated; pass data_grads=True)")
     M, C, J, b, T, mask = solver.prepare(M, C, J, b, T, mask)
-    x, status = _OSCSolve.apply(solver, M, C, J, b, T, mask)
+    fn = _OSCSolveData if data_grads else _OSCSolve
+    x, status = fn.apply(solver, M, C, J, b, T, mask)
     d = solver.dims
     return x[:, d["nv"]:d["nv"] + d["nu"]], x, status

@@ -28,7 +28,8 @@ ARCH = os.environ.get("OSC_OFFLOAD_ARCH", "gfx950")
 # kernel units (csrc/osc_device.hpp lists what each holds) + host units
 SOURCES = ["osc_ipm_go2.hip", "osc_ipm_walter.hip", "osc_ipm_wheels.hip", "osc_multi.hip",
            "osc_setup.hip", "osc_gi.hip", "osc_dual.hip", "osc_kinematics.hip",
-           "osc_producers.hip", "osc_rollout.hip", "osc_backward.hip", "osc_api.hip",
+           "osc_producers.hip", "osc_rollout.hip", "osc_backward.hip", "osc_backward_data.hip",
+           "osc_api.hip",
            "osc_model.cpp", "osc_mjcf.cpp", "osc_host_feed.cpp"]
 # every header of csrc/ (the up-to-date check's dependency list: a new header is picked up by name)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp"))

@@ -205,6 +205,31 @@ class OSCBatchSolver:
         if rc != 0:
             raise _lib.OSCError("osc_batch_solve_backward", rc)
 
+    def backward_data_into(self, out: SolveResult, M, J, b, T, mask, grad_x, grad_M=None,
+                           grad_C=None, grad_J=None, grad_wrow=None, grad_T=None, grad_b=None,
+                           stream=None) -> None:
+        """Launch only: osc_batch_solve_backward_data (include/osc_backward.h).  From grad_x =
+        dL/dx (nenv, nv + nu + 3 nc): dL/dM into grad_M (nenv, nv, nv), dL/dC into grad_C
+        (nenv, nv), dL/dJ into grad_J (nenv, 6 ns, nv), the per-row weight gradient into grad_wrow
+        (nenv, 6 ns; a site's w_pos / w_rot gradient is the sum of its three rows), dL/dT into
+        grad_T (nenv, ns, 6) and dL/db into grad_b (nenv, 6 ns) -- each None or a tensor; a None
+        is not computed.  `out` is the SolveResult of the forward solve_into with x and y on the
+        same M, J, b, T and mask; its workspace must not have been reused since.  An env whose
+        status is not 0 gets zeros."""
+        if out.x is None or out.y is None or out.workspace is None:
+            raise ValueError("backward_data_into needs the forward solve's design vector, duals "
+                             "and workspace (alloc_outputs(want_x=True, want_y=True))")
+        nenv = out.tau.shape[0]
+        s = (torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = _lib.lib().osc_batch_solve_backward_data(
+            self._h, nenv, ptr(M), ptr(J), ptr(b), ptr(T), ptr(mask), ptr(out.x), ptr(out.y),
+            ptr(out.status), ptr(grad_x), ptr(grad_M), ptr(grad_C), ptr(grad_J), ptr(grad_wrow),
+            ptr(grad_T), ptr(grad_b), ptr(out.workspace),
+            ctypes.c_size_t(out.workspace.numel() * 8), ctypes.c_void_p(s))
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_solve_backward_data", rc)
+
     def alloc_warm_state(self, nenv: int) -> torch.Tensor:
         """Zero-filled warm state (osc_warm_state_bytes): every env starts cold on its first tick."""
         nb = ctypes.c_size_t()
