@@ -78,6 +78,11 @@ __device__ __forceinline__ void ipm_block(
   // (so does a model with wheel rows: its LDS block holds the rows A~ instead)
   constexpr bool kRefG = RF == kRfFused && (!SMALL || D::WH);
   constexpr bool WHR = D::WH && RF == kRfFused;   // the wheel rows' rotated Newton systems
+  // the one-wave fused refinement with X in Hr's LDS region (Go2): its steps scheduled for a lone
+  // wavefront, bitwise the general steps' results.  (WaLTER's one-wave kernels, NV <= 16 and no
+  // second dot-product pass to fold, keep the general steps: with these they measured 0.5 %
+  // slower and spilled 12 more SGPRs, profiles/r09/refine/)
+  constexpr bool kLean = kXinHr && !kRefG;
   using WL = WheelLds<D>;
   WheelRot W = wheel_rot<D>(B + LY::IL);   // (osc_ipm_wheel.hpp; dead without wheel rows)
   // Hr columns are addressed as wave-uniform base (SGPR pair) + 32-bit lane offset + immediate:
@@ -948,6 +953,106 @@ __device__ __forceinline__ void ipm_block(
         STAMP_END(8);   // (the loop's slot 8 doubles as the refinement's LDL)
         STAMP_BEGIN();
         conv = false;
+        if constexpr (kLean) {
+        for (int k = 0; k < kRefineMaxSteps; ++k) {
+          // One wave, [X | H_dv | f_dv] in LDS: the same chains per output element as the general
+          // step below, scheduled for a lone wavefront, which waits out every LDS hand-off and
+          // every branch alone (DESIGN.md §5 "The refinement's steps").  Four hand-offs (y -> dv ->
+          // gx -> r, d -> mu) where the general step has seven; the rows' products branch-free
+          // (Gv_all); both row-space vectors stored at the top -- they need nothing of this step
+          // (sDr is free here: gx goes to dv's slot, whose reads precede its store in program order)
+          // -- so both G' products read beside the X'gx operands; and the rows past the 16th as
+          // second chains of the lanes' own loops (their row clamped, their store masked), not as
+          // an exec-masked pass of their own.
+          constexpr int NT = (NV + kRow - 1) / kRow;
+          double R3[NRL];
+          {
+            double g3[NRL];
+            Gv_all<D>(L, act, sVy, g3);
+#pragma unroll
+            for (int t = 0; t < NRL; ++t) {
+              R3[t] = (Dr[t] != 0.0) ? g3[t] - h[t] : 0.0;
+              sVr[l + kRow * t] = mur[t];
+              sDr[l + kRow * t] = Dr[t] * R3[t];
+            }
+          }
+          int rr[NT];
+          double acc[NT];
+#pragma unroll
+          for (int t = 0; t < NT; ++t) {
+            rr[t] = (l + kRow * t < NV) ? l + kRow * t : 0;   // (a lane past NV: row 0, unused)
+            acc[t] = rX[rr[t] * NY1P + NY];
+          }
+          static_assert(NY % 2 == 0 && LY::I_VY % 2 == 0, "y read as 16-byte pairs");
+#pragma unroll
+          for (int i = 0; i < NY; i += 2) {
+            const double2 yy = *reinterpret_cast<const double2*>(sVy + i);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+              acc[t] = fma(rX[rr[t] * NY1P + i], yy.x, acc[t]);
+              acc[t] = fma(rX[rr[t] * NY1P + i + 1], yy.y, acc[t]);
+            }
+          }
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+            if (l + kRow * t < NV) sXb[l + kRow * t] = acc[t];
+          wave_sync();
+#pragma unroll
+          for (int t = 0; t < NT; ++t) acc[t] = rG[rr[t]];
+#pragma unroll
+          for (int i = 0; i < NV; ++i) {
+            const double di = sXb[i];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = fma(rH[rr[t] * NV + i], di, acc[t]);
+          }
+          wave_sync();
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+            if (l + kRow * t < NV) sXb[l + kRow * t] = acc[t];
+          wave_sync();
+          double r0 = (j0 < NU ? wu : wz) * ya0, r1 = (jj1 < NU ? wu : wz) * ya1;
+#pragma unroll
+          for (int i = 0; i < NV; ++i) {
+            r0 = fma(rX[i * NY1P + j0], sXb[i], r0);
+            r1 = fma(rX[i * NY1P + jj1], sXb[i], r1);
+          }
+          double gm0, gm1, b0, b1;
+          GTw2<D, SMALL>(L, sVr, gm0, gm1);
+          GTw2<D, SMALL>(L, sDr, b0, b1);
+          r0 += gm0;
+          r1 += gm1;
+          double d0 = -r0 - b0, d1 = -r1 - b1;
+          ldl_solve_rows<NY>(c0, c1, dinv0, dinv1, d0, d1, l);
+          const bool frz = conv;   // converged at an earlier step: no further move
+          if (frz) {
+            d0 = 0.0;
+            d1 = 0.0;
+          }
+          sVy2[j0] = d0;
+          if (v1) sVy2[j1] = d1;
+          wave_sync();
+          {
+            double gd[NRL];
+            Gv_all<D>(L, act, sVy2, gd);
+#pragma unroll
+            for (int t = 0; t < NRL; ++t) {
+              double inc = Dr[t] * (gd[t] + R3[t]);
+              in_vgpr(inc);   // (a product, then a sum: never one fma with mur)
+              mur[t] += frz ? 0.0 : inc;
+            }
+          }
+          ya0 += d0;
+          ya1 += d1;
+          sVy[j0] = ya0;
+          if (v1) sVy[j1] = ya1;
+          wave_sync();
+          // (the general step's convergence test)
+          const double dn = row_max(fmax(fabs(d0), v1 ? fabs(d1) : 0.0));
+          if (!frz) dlast = dn;
+          conv = conv || (k + 1 >= refine_steps && dn <= 1e-10 * (1.0 + yscale));
+          if (k + 1 >= refine_steps && __ballot(mine && !conv) == 0) break;
+        }
+        } else
         for (int k = 0; k < (kOldWh ? refine_steps : kRefineMaxSteps); ++k) {
           // WH: X holds X^ = X'T, so dv = X^ [y^; 1] (y^ = T'y staged in sVy2, free until the step)
           // and the rows' residual at y comes with y^
@@ -1105,9 +1210,10 @@ __device__ __forceinline__ void ipm_block(
         // envs at joint_range 1.0, tests/golden/go2_unrefined_joint_states.npz; tools/kkt_study.py
         // one_change: every such env settles in <= 4 rounds on its exact optimum)
         double nviol = 0.0, vl = 0.0, gv[NRL];
+        if constexpr (kLean) Gv_all<D>(L, act, sVy, gv);
 #pragma unroll
         for (int t = 0; t < NRL; ++t) {
-          gv[t] = Gv<D>(L, act, sVy, t) - h[t];
+          gv[t] = (kLean ? gv[t] : Gv<D>(L, act, sVy, t)) - h[t];
           vl = fmax(vl, (act[t] && Dr[t] == 0.0 && gv[t] > ytol) ? gv[t] : 0.0);
         }
         const double vbest = WHR ? 0.0 : row_max(vl);
