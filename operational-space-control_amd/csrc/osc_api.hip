@@ -39,6 +39,7 @@
 //                     complementarity) are 16-lane DPP butterflies.
 #include "osc_internal.hpp"
 #include "osc_kin_model.hpp"
+#include "osc_env_params.h"
 #include "osc_mixed.h"
 
 using namespace osc;
@@ -290,7 +291,13 @@ void launch_t(LaunchArgs a, unsigned stages, const QposArgs* q) {
       }
     }
 #endif
-    if (q == nullptr) launch_setup<D>(a);
+    // (per-env task weights: the assembly's ENV variant, only when the call carries any)
+    bool env_w = false;
+    if constexpr (!D::WH) env_w = a.ep.w_pos != nullptr || a.ep.w_rot != nullptr;
+    if constexpr (!D::WH) {
+      if (env_w) launch_setup_env<D>(a);
+    }
+    if (q == nullptr && !env_w) launch_setup<D>(a);
   }
   if (!(stages & kInteriorPoint)) return;
   // Wheel-row models run the active-set fallback over the envs the interior point left
@@ -301,6 +308,18 @@ void launch_t(LaunchArgs a, unsigned stages, const QposArgs* q) {
   // (and so does the cold solve's fix-up pass in the interior-point launch, refinement fused)
   if (a.status == nullptr && (a.warm != nullptr || fallback || a.model->refine))
     a.status = reinterpret_cast<int32_t*>(a.ws + static_cast<size_t>(D::WS) * a.nenv);
+  // (per-env mu, torque box or fz bounds: the interior point's and the dual kernel's ENV variants)
+  bool env_c = false;
+  if constexpr (!D::WH)
+    env_c = a.ep.mu != nullptr || a.ep.u_lb != nullptr || a.ep.u_ub != nullptr ||
+            a.ep.fz_lb != nullptr || a.ep.fz_ub != nullptr;
+  if constexpr (!D::WH) {
+    if (env_c) {
+      launch_ipm_env<D>(a);
+      if (a.y != nullptr) launch_dual_env<D>(a);
+      return;
+    }
+  }
   launch_ipm<D>(a);
   if constexpr (D::WH) {
     if (fallback) launch_gi<D>(a);
@@ -320,7 +339,8 @@ int launch(const osc_model* model, int32_t nenv, const double* M, const double* 
            const double* b, const double* T, const double* contact_mask, double* tau, double* x,
            int32_t* status, int32_t* iters, void* workspace, size_t workspace_bytes,
            void* stream, unsigned stages, double* warm = nullptr, const double* wdir = nullptr,
-           double* y = nullptr, const QposArgs* q = nullptr) {
+           double* y = nullptr, const QposArgs* q = nullptr,
+           const osc_env_params* ep = nullptr) {
   if (!model || nenv < 0) return OSC_ERR_INVALID_ARGUMENT;
   if (nenv == 0) return OSC_OK;
   if (!on_model_device(model)) return OSC_ERR_INVALID_ARGUMENT;
@@ -356,6 +376,8 @@ int launch(const osc_model* model, int32_t nenv, const double* M, const double* 
   int rc = OSC_OK;
   LaunchArgs a{model, nenv, M, C, J, b, T, contact_mask, tau, x, status, iters, ws, warm, s,
                wdir, y};
+  if (ep != nullptr)   // (an all-NULL block chooses no per-env kernel: launch_t)
+    a.ep = EnvPtrs{ep->mu, ep->u_lb, ep->u_ub, ep->fz_lb, ep->fz_ub, ep->w_pos, ep->w_rot};
   switch (model->kid) {
     case K_GO2:
       launch_t<Go2>(a, stages, q);
@@ -701,4 +723,88 @@ extern "C" int osc_batch_solve_assembled(const osc_model* model, int32_t nenv,
   return launch(model, nenv, nullptr, nullptr, nullptr, nullptr, nullptr, contact_mask, tau, x,
                 status, iters, workspace, workspace_bytes, stream,
                 kInteriorPoint);
+}
+
+// ---- per-env parameters (include/osc_env_params.h) ----
+namespace {
+// What every _env entry refuses before anything is enqueued: a model with wheel rows (their
+// kernels and fallback have no per-env variant), one without the refinement (refine_steps = 0:
+// the unfused pass sequence has none either), wheel directions, a misaligned array.
+bool env_call_ok(const osc_model* model, const osc_env_params* ep, const osc_solve_extras* extras) {
+  if (!model || model->kid == K_WALTER_WHEELS || !model->refine) return false;
+  if (extras && extras->wheel_dir) return false;
+  if (ep != nullptr)
+    for (const double* p : {ep->mu, ep->u_lb, ep->u_ub, ep->fz_lb, ep->fz_ub, ep->w_pos, ep->w_rot})
+      if ((reinterpret_cast<uintptr_t>(p) & 7u) != 0) return false;
+  return true;
+}
+}  // namespace
+
+extern "C" int osc_batch_solve_env(const osc_model* model, int32_t nenv, const double* M,
+                                   const double* C, const double* J, const double* b,
+                                   const double* T, const double* contact_mask,
+                                   const osc_env_params* env_params, const osc_solve_extras* extras,
+                                   double* tau, double* x, int32_t* status, int32_t* iters,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (!env_call_ok(model, env_params, extras)) return OSC_ERR_INVALID_ARGUMENT;
+  return launch(model, nenv, M, C, J, b, T, contact_mask, tau, x, status, iters, workspace,
+                workspace_bytes, stream, kBoth, nullptr, nullptr, extras ? extras->y : nullptr,
+                nullptr, env_params);
+}
+
+extern "C" int osc_batch_solve_warm_env(const osc_model* model, int32_t nenv, const double* M,
+                                        const double* C, const double* J, const double* b,
+                                        const double* T, const double* contact_mask,
+                                        const osc_env_params* env_params,
+                                        const osc_solve_extras* extras, double* tau, double* x,
+                                        int32_t* status, int32_t* iters, double* warm_state,
+                                        size_t warm_state_bytes, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  if (!env_call_ok(model, env_params, extras) ||
+      !warm_small(model, nenv, warm_state, warm_state_bytes))
+    return OSC_ERR_INVALID_ARGUMENT;
+  return launch(model, nenv, M, C, J, b, T, contact_mask, tau, x, status, iters, workspace,
+                workspace_bytes, stream, kBoth, warm_state, nullptr, extras ? extras->y : nullptr,
+                nullptr, env_params);
+}
+
+extern "C" int osc_batch_assemble_env(const osc_model* model, int32_t nenv, const double* M,
+                                      const double* C, const double* J, const double* b,
+                                      const double* T, const double* contact_mask,
+                                      const osc_env_params* env_params,
+                                      const osc_solve_extras* extras, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  if (!env_call_ok(model, env_params, extras)) return OSC_ERR_INVALID_ARGUMENT;
+  return launch(model, nenv, M, C, J, b, T, contact_mask, nullptr, nullptr, nullptr, nullptr,
+                workspace, workspace_bytes, stream, kAssemble, nullptr, nullptr, nullptr, nullptr,
+                env_params);
+}
+
+extern "C" int osc_batch_solve_assembled_env(const osc_model* model, int32_t nenv,
+                                             const double* contact_mask,
+                                             const osc_env_params* env_params,
+                                             const osc_solve_extras* extras, double* tau, double* x,
+                                             int32_t* status, int32_t* iters, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  if (!env_call_ok(model, env_params, extras)) return OSC_ERR_INVALID_ARGUMENT;
+  // (duals: refused by launch, as in every split call -- the dual kernel needs M and J)
+  return launch(model, nenv, nullptr, nullptr, nullptr, nullptr, nullptr, contact_mask, tau, x,
+                status, iters, workspace, workspace_bytes, stream, kInteriorPoint, nullptr, nullptr,
+                extras ? extras->y : nullptr, nullptr, env_params);
+}
+
+extern "C" int osc_batch_solve_assembled_warm_env(const osc_model* model, int32_t nenv,
+                                                  const double* contact_mask,
+                                                  const osc_env_params* env_params,
+                                                  const osc_solve_extras* extras, double* tau,
+                                                  double* x, int32_t* status, int32_t* iters,
+                                                  double* warm_state, size_t warm_state_bytes,
+                                                  void* workspace, size_t workspace_bytes,
+                                                  void* stream) {
+  if (!env_call_ok(model, env_params, extras) ||
+      !warm_small(model, nenv, warm_state, warm_state_bytes))
+    return OSC_ERR_INVALID_ARGUMENT;
+  return launch(model, nenv, nullptr, nullptr, nullptr, nullptr, nullptr, contact_mask, tau, x,
+                status, iters, workspace, workspace_bytes, stream, kInteriorPoint, warm_state,
+                nullptr, extras ? extras->y : nullptr, nullptr, env_params);
 }

@@ -11,10 +11,13 @@
 //                                                         osc_ipm_rows.hpp (inequality rows),
 //                                                         osc_ipm_wheel.hpp (wheel rotations),
 //                                                         osc_ipm_launch.hpp (kernels, launch_ipm)
-//   osc_dual.hip        kernel 3  osc_dual_kernel        (dual solution, optional)
+//   osc_dual.hip        kernel 3  osc_dual_kernel        (dual solution, optional; its body:
+//                                                         osc_dual_body.hpp)
+//   (kernels 1-3 have per-env-parameter variants, osc_*_env_kernel: include/osc_env_params.h)
 //   osc_gi.hip          kernel 4  osc_gi_kernel          (wheel-row active-set fallback)
 //   osc_multi.hip       the two-model grids of osc_batch_solve_multi / osc_batch_tick_multi
-//   osc_api.hip         the C-ABI (include/osc_batch.h): models, tuning, launch sequencing
+//   osc_api.hip         the C-ABI (include/osc_batch.h, osc_env_params.h): models, tuning, launch
+//                       sequencing
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,6 +66,13 @@ struct DevParams {
   unsigned long long* stamps;        // diagnostic builds: [kStampBlocks][kStampSlots], IPM phases
   unsigned long long* setup_stamps;  // ... and the assembly's (one buffer for every kernel unit)
 #endif
+};
+
+// Per-env parameters (include/osc_env_params.h's osc_env_params, the _env entry points): device
+// arrays that replace DevParams' mu, u_lb / u_ub, z_lb[2] / z_ub[2] and w_row env by env, each
+// nullable (= the model's value).  Passed to the kernels' ENV variants by value.
+struct EnvPtrs {
+  const double *mu, *u_lb, *u_ub, *fz_lb, *fz_ub, *w_pos, *w_rot;
 };
 
 // Full-space refinement: at most kRefineRounds active-set rounds of at most kRefineMaxSteps

@@ -35,6 +35,8 @@ struct LaunchArgs {
   hipStream_t s;
   const double* wdir;    // wheel directions (wheel-row models)
   double* y;             // duals, nullable
+  EnvPtrs ep = {};       // the _env entry points' arrays (include/osc_env_params.h); all NULL =
+                         // the model's values, the kernels without per-env reads
 };
 
 template <class D> void launch_setup(const LaunchArgs& a);   // osc_setup.hip
@@ -43,6 +45,10 @@ template <class D> void launch_setup_qpos(const LaunchArgs& a, const QposArgs& q
 template <class D> void launch_ipm(const LaunchArgs& a);     // osc_ipm_<model>.hip
 template <class D> void launch_dual(const LaunchArgs& a);    // osc_dual.hip
 template <class D> void launch_gi(const LaunchArgs& a);      // osc_gi.hip
+// the per-env variants of the three above (a.ep; models without wheel rows)
+template <class D> void launch_setup_env(const LaunchArgs& a);
+template <class D> void launch_ipm_env(const LaunchArgs& a);
+template <class D> void launch_dual_env(const LaunchArgs& a);
 // osc_multi.hip: WaLTER's job and Go2's job in one assembly grid and one interior-point grid
 void launch_pair_walter_go2(const osc_batch_job& w, const osc_batch_job& g, hipStream_t s);
 
@@ -80,5 +86,11 @@ extern template void launch_dual<Go2>(const LaunchArgs&);
 extern template void launch_dual<Walter>(const LaunchArgs&);
 extern template void launch_dual<WalterW>(const LaunchArgs&);
 extern template void launch_gi<WalterW>(const LaunchArgs&);
+extern template void launch_setup_env<Go2>(const LaunchArgs&);
+extern template void launch_setup_env<Walter>(const LaunchArgs&);
+extern template void launch_ipm_env<Go2>(const LaunchArgs&);
+extern template void launch_ipm_env<Walter>(const LaunchArgs&);
+extern template void launch_dual_env<Go2>(const LaunchArgs&);
+extern template void launch_dual_env<Walter>(const LaunchArgs&);
 
 }  // namespace osc

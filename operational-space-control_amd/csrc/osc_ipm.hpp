@@ -21,12 +21,18 @@ namespace osc {
 // doubles of LDS.  Wrapped by osc_ipm_kernel (one model) and osc_ipm_pair_kernel (two models).
 // WARM = false compiles none of the warm-start / fix-up logic (the cold solve's register budget
 // is unchanged by it: the two-wave Go2 variant would otherwise spill more).
-template <class D, bool SMALL, bool WARM, int RF_ = kRfNone, int CP = kCpNone>
+// ENV = true (the _env entry points, include/osc_env_params.h): mu, the torque box and the fz
+// bounds of each env come from EP's arrays (a NULL one: the model's value) in the row set-up below,
+// the only place that reads them; an env whose values are invalid is poisoned there with a NaN
+// gradient and ends OSC_SOLVE_NUMERICAL like an env with NaN inputs.  ENV = false compiles none of
+// it: the existing kernels' code is unchanged.
+template <class D, bool SMALL, bool WARM, int RF_ = kRfNone, int CP = kCpNone, bool ENV = false>
 __device__ __forceinline__ void ipm_block(
     const DevParams* __restrict__ P, int blk, int nenv, const double* __restrict__ gmask,
     const double* __restrict__ ws, double* __restrict__ gtau, double* __restrict__ gx,
     int32_t* __restrict__ gstatus, int32_t* __restrict__ giters, double* __restrict__ gwarm,
-    int flags, double* __restrict__ sm, ParkArgs PA = ParkArgs{}) {
+    int flags, double* __restrict__ sm, ParkArgs PA = ParkArgs{}, EnvPtrs EP = EnvPtrs{}) {
+  static_assert(!ENV || (CP == kCpNone && !D::WH), "per-env parameters: no compaction, no wheel rows");
   static_assert(CP == kCpNone || (!WARM && RF_ == kRfFused && !D::WH),
                 "compaction: cold solves with the fused refinement only");
   constexpr int NV = D::NV, NU = D::NU, NC = D::NC, NY = D::NY, NY1P = D::NY1P, MI = D::MI,
@@ -187,6 +193,18 @@ __device__ __forceinline__ void ipm_block(
   // kind (torque bound q / sign, or contact k / pyramid side) is recomputed from r. ----
   bool act[NRL];
   double h[NRL];
+  // ENV: this env's friction and fz bounds (every lane of the row reads the same address) and
+  // their validity; the torque box is checked joint by joint in the loop (each lane holds one side
+  // of a joint's box and reads both)
+  double env_mu = 0.0, env_zl = 0.0, env_zu = 0.0;
+  bool env_bad = false;
+  if constexpr (ENV) {
+    const size_t e = static_cast<size_t>(env);
+    env_mu = EP.mu ? EP.mu[e] : P->mu;
+    env_zl = EP.fz_lb ? EP.fz_lb[e] : P->z_lb[2];
+    env_zu = EP.fz_ub ? EP.fz_ub[e] : P->z_ub[2];
+    env_bad = !isfinite(env_mu) || env_zl != env_zl || env_zu != env_zu;
+  }
 #pragma unroll
   for (int t = 0; t < NRL; ++t) {
     const int r = l + kRow * t;
@@ -195,7 +213,16 @@ __device__ __forceinline__ void ipm_block(
     if (r < 2 * NU) {
       const int q = r >> 1;
       const double sg = (r & 1) ? -1.0 : 1.0;
-      const double bnd = (r & 1) ? P->u_lb[q] : P->u_ub[q];
+      double bnd;
+      if constexpr (ENV) {
+        const size_t eq = static_cast<size_t>(env) * NU + q;
+        const double lbq = EP.u_lb ? EP.u_lb[eq] : P->u_lb[q];
+        const double ubq = EP.u_ub ? EP.u_ub[eq] : P->u_ub[q];
+        env_bad = env_bad || !(lbq < ubq);   // (what osc_model_create refuses; a NaN fails it too)
+        bnd = (r & 1) ? lbq : ubq;
+      } else {
+        bnd = (r & 1) ? P->u_lb[q] : P->u_ub[q];
+      }
       act[t] = fabs(bnd) < P->inf_thresh;
       h[t] = sg * bnd;                                     // the row is +-y_q
     } else if (r < MI) {
@@ -205,18 +232,19 @@ __device__ __forceinline__ void ipm_block(
         if (rt < 4) {
           act[t] = true;                                   // friction pyramid, bineq = 0
         } else if (rt == 4) {
-          const double lb = P->z_lb[2] * m;                // -fz <= -lb
+          const double lb = (ENV ? env_zl : P->z_lb[2]) * m;   // -fz <= -lb
           act[t] = fabs(lb) < P->inf_thresh;
           h[t] = -lb;
         } else {
-          const double ub = P->z_ub[2] * m;                // fz <= ub
+          const double ub = (ENV ? env_zu : P->z_ub[2]) * m;   // fz <= ub
           act[t] = fabs(ub) < P->inf_thresh;
           h[t] = ub;
         }
       }
     }
   }
-  const double mu_f = P->mu;
+  const double mu_f = ENV ? env_mu : P->mu;
+  if constexpr (ENV) env_bad = row_max(env_bad ? 1.0 : 0.0) != 0.0;   // the env's 16 lanes agree
   // Rows of the initial least-squares fit (Hr + G'G) y0 = -g + G'h: every active row except
   // fz <= big_number, which would drag fz to ~big_number/2 together with fz >= 0 and start
   // the torque rows far outside their box (tools/ipm_model.py "y0_nofz": Go2 lockstep
@@ -301,7 +329,9 @@ __device__ __forceinline__ void ipm_block(
   const double hdg1 =
       HRL ? sHr[jj1 * NY + jj1] : wsw[lane_off + static_cast<unsigned>(hr_off<D>(jj1, jj1))];
   load_hr();
-  const double g0 = sG[j0], g1 = sG[jj1];
+  // (ENV: an invalid env's gradient is NaN -- every iterate of it is, its wave-mates' never)
+  const double g0 = (ENV && env_bad) ? __builtin_nan("") : sG[j0],
+               g1 = (ENV && env_bad) ? __builtin_nan("") : sG[jj1];
   double y0 = 0.0, y1 = 0.0;
   double s[NRL], lam[NRL];
 #pragma unroll

@@ -4,4 +4,5 @@
 
 namespace osc {
 template void launch_ipm<Go2>(const LaunchArgs&);
+template void launch_ipm_env<Go2>(const LaunchArgs&);   // (the per-env variants)
 }  // namespace osc

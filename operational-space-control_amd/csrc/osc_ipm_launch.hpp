@@ -62,6 +62,40 @@ __global__ __launch_bounds__(kWave, SMALL ? 1 : 2) void osc_refine_kernel(
                                    gstatus, nullptr, nullptr, 0, sm);
 }
 
+// The _env entry points' kernels (include/osc_env_params.h): osc_ipm_kernel's and
+// osc_refine_kernel's bodies with ipm_block's ENV on and the per-env arrays by value.  Kernels of
+// their own, so the ones above keep their names, arguments and code.
+template <class D, bool SMALL, bool WARM, int RF>
+__global__ __launch_bounds__(kWave, SMALL ? 1 : OSC_LARGE_WAVES) void osc_ipm_env_kernel(
+    const DevParams* __restrict__ P, int nenv, const double* __restrict__ gmask,
+    const double* __restrict__ ws, double* __restrict__ gtau, double* __restrict__ gx,
+    int32_t* __restrict__ gstatus, int32_t* __restrict__ giters, double* __restrict__ gwarm,
+    int flags, EnvPtrs EP) {
+  static_assert(!D::WH, "per-env parameters: no wheel rows");
+  __shared__ __attribute__((aligned(16))) double sm[ipm_lds_doubles<D, SMALL, RF>()];
+  ipm_block<D, SMALL, WARM, RF, kCpNone, true>(P, static_cast<int>(blockIdx.x), nenv, gmask, ws,
+                                               gtau, gx, gstatus, giters, gwarm, flags & 3, sm,
+                                               ParkArgs{}, EP);
+  if constexpr (WARM || RF == kRfFused) {
+    if (flags & 4) {   // the cold fix-up pass in the same launch (osc_ipm_kernel)
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      ipm_block<D, SMALL, WARM, RF, kCpNone, true>(P, static_cast<int>(blockIdx.x), nenv, gmask,
+                                                   ws, gtau, gx, gstatus, giters, gwarm,
+                                                   (flags & 2) | 1, sm, ParkArgs{}, EP);
+    }
+  }
+}
+template <class D, bool SMALL>
+__global__ __launch_bounds__(kWave, SMALL ? 1 : 2) void osc_refine_env_kernel(
+    const DevParams* __restrict__ P, int nenv, const double* __restrict__ gmask,
+    const double* __restrict__ ws, double* __restrict__ gtau, double* __restrict__ gx,
+    int32_t* __restrict__ gstatus, EnvPtrs EP) {
+  __shared__ __attribute__((aligned(16))) double sm[ipm_lds_doubles<D, SMALL, kRfOnly>()];
+  ipm_block<D, SMALL, false, kRfOnly, kCpNone, true>(P, static_cast<int>(blockIdx.x), nenv, gmask,
+                                                     ws, gtau, gx, gstatus, nullptr, nullptr, 0, sm,
+                                                     ParkArgs{}, EP);
+}
+
 // Two models' interior point in one grid, one wavefront per SIMD (the one-wave variant of both):
 // blocks [0, nbA) are model A's wavefronts, the rest model B's.  The dispatcher hands out blocks
 // in order, so with the slower model first the faster model's wavefronts fill the SIMDs that
@@ -194,6 +228,36 @@ void launch_ipm(const LaunchArgs& a) {
         warm_pass(1);
       }
     }
+  }
+}
+
+// ---- launch_ipm_env: launch_ipm's pass sequence with the per-env kernels ----
+// (models with the refinement on and no wheel rows: the entries refuse the others.)  No lockstep
+// compaction: its park and resume kernels have no per-env variant -- the results are bitwise the
+// single pass's (tests/test_gpu_stages.py), only the throughput of cold batches from kParkMinRounds
+// rounds of wavefronts per SIMD differs.
+template <class D, bool SMALL, bool WARM, int RF>
+void ipm_env_launch(const LaunchArgs& a, unsigned nb, int flags) {
+  hipLaunchKernelGGL((osc_ipm_env_kernel<D, SMALL, WARM, RF>), dim3(nb), dim3(kWave), 0, a.s,
+                     a.model->dparams, a.nenv, a.mask, a.ws, a.tau, a.x, a.status, a.iters,
+                     WARM ? a.warm : nullptr, flags, a.ep);
+}
+template <class D>
+void launch_ipm_env(const LaunchArgs& a) {
+  const unsigned nb = static_cast<unsigned>((a.nenv + kEnvPerWave - 1) / kEnvPerWave);
+  const int flags = a.y != nullptr ? 2 : 0;
+  const bool small = a.nenv <= a.model->small_batch_max;
+  if (a.warm == nullptr) {          // cold: refinement and fix-up pass fused, one launch
+    with_small(small, [&](auto S) {
+      ipm_env_launch<D, decltype(S)::value, false, kRfFused>(a, nb, flags | 4);
+    });
+  } else if (small) {               // warm, one wave per SIMD: the same
+    ipm_env_launch<D, true, true, kRfFused>(a, nb, 4);
+  } else {                          // warm past it: warm pass, refinement pass, cold fix-up pass
+    ipm_env_launch<D, false, true, kRfNone>(a, nb, 0);
+    hipLaunchKernelGGL((osc_refine_env_kernel<D, false>), dim3(nb), dim3(kWave), 0, a.s,
+                       a.model->dparams, a.nenv, a.mask, a.ws, a.tau, a.x, a.status, a.ep);
+    ipm_env_launch<D, false, true, kRfFused>(a, nb, 1);
   }
 }
 

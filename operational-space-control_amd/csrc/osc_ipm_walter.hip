@@ -4,4 +4,5 @@
 
 namespace osc {
 template void launch_ipm<Walter>(const LaunchArgs&);
+template void launch_ipm_env<Walter>(const LaunchArgs&);   // (the per-env variants)
 }  // namespace osc

@@ -17,7 +17,17 @@ void launch_setup(const LaunchArgs& a) {
                      a.nenv, a.M, a.C, a.J, a.b, a.T, a.mask, a.ws, a.wdir);
 }
 
+// the _env entry points: the same grid with the per-env task weights (a.ep.w_pos / w_rot)
+template <class D>
+void launch_setup_env(const LaunchArgs& a) {
+  const dim3 grid(static_cast<unsigned>(a.nenv));
+  hipLaunchKernelGGL((osc_setup_env_kernel<D, !D::JG>), grid, dim3(kWave), 0, a.s, a.model->dparams,
+                     a.nenv, a.M, a.C, a.J, a.b, a.T, a.mask, a.ws, a.ep);
+}
+
 template void launch_setup<Go2>(const LaunchArgs&);
+template void launch_setup_env<Go2>(const LaunchArgs&);
+template void launch_setup_env<Walter>(const LaunchArgs&);
 template void launch_setup<Walter>(const LaunchArgs&);
 template void launch_setup<WalterW>(const LaunchArgs&);
 

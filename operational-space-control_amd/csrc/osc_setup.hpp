@@ -113,14 +113,26 @@ __device__ __noinline__ void wave_mgs_lds(double* rows, int lane, double drop, d
 // past one round of interior-point waves only (4,096: 0.1646 vs 0.1620 ms, when LDS still capped
 // a CU at 11 waves; profiles/r05/ab_setup_unroll4.jsonl); with the LDS cut it wins at every size
 // (profiles/r06/lean_lds/).
-template <class D, bool KIN = false, bool LEAN = false>
+// ENV = true (the _env entry points, include/osc_env_params.h; QP-input form only): the task-row
+// weights are the env's own -- row r of site k takes EP.w_pos[env][k] (translational half) or
+// EP.w_rot[env][k], a NULL array the model's w_row -- and a non-finite one becomes NaN, so that the
+// env's reduced QP is NaN and its solve ends OSC_SOLVE_NUMERICAL.  ENV = false compiles none of it.
+template <class D>
+__device__ __forceinline__ double env_w_row(const DevParams* __restrict__ P, const EnvPtrs& EP,
+                                            int env, int r) {
+  const double* a = r < 3 * D::NS ? EP.w_pos : EP.w_rot;
+  const double w = a ? a[static_cast<size_t>(env) * D::NS + (r % (3 * D::NS)) / 3] : P->w_row[r];
+  return isfinite(w) ? w : __builtin_nan("");
+}
+template <class D, bool KIN = false, bool LEAN = false, bool ENV = false>
 __device__ __forceinline__ void setup_env(
     const DevParams* __restrict__ P, int env, int nenv, const double* __restrict__ gM,
     const double* __restrict__ gC, const double* __restrict__ gJ, const double* __restrict__ gb,
     const double* __restrict__ gT, const double* __restrict__ gmask, double* __restrict__ ws,
     double* __restrict__ sm, const double* __restrict__ gwd,
     const osc_kin::KinDev* __restrict__ Kg = nullptr, const double* __restrict__ gqpos = nullptr,
-    const double* __restrict__ gqvel = nullptr) {
+    const double* __restrict__ gqvel = nullptr, EnvPtrs EP = EnvPtrs{}) {
+  static_assert(!ENV || (!KIN && !D::WH), "per-env weights: QP inputs, no wheel rows");
   constexpr int NV = D::NV, NU = D::NU, NC = D::NC, NS = D::NS, NB = D::NB, NY = D::NY,
                 NY1 = D::NY1, NY1P = D::NY1P, S = D::S, NA = D::NA;
   const int lane = threadIdx.x;
@@ -136,6 +148,17 @@ __device__ __forceinline__ void setup_env(
   double* sX = sm + (kHaG ? D::O_X_L : D::O_X);
   double* sU = sX + NB * NY1P;   // U parked in X's last rows until X replaces it
   double* sMask = sm + (kHaG ? D::O_MASK_L : D::O_MASK);
+
+  // ENV, the VALU path of phase B: the env's 2 NS site weights [w_pos | w_rot] go to LDS once
+  // (behind the block's own layout: osc_setup_env_kernel) and phase B's row loop reads row r's
+  // from there -- a global load per row in that loop made the Go2 assembly 18 % slower (32.4 vs
+  // 27.5 us at 4,096 envs)
+  double* sW = sm + (LEAN ? D::SMEM_L : D::SMEM);
+  if constexpr (ENV && !D::JG) {
+    static_assert(2 * NS <= kWave, "one lane per site weight");
+    if (lane < 2 * NS) sW[lane] = env_w_row<D>(P, EP, env, 3 * lane);   // (stored ahead of phase A's
+  }                                                                      // wave_sync)
+  (void)sW;
 
   STAMP_DECL
   STAMP_BEGIN();
@@ -174,7 +197,8 @@ __device__ __forceinline__ void setup_env(
       const int half = r / (3 * NS), rr = r % (3 * NS);
       ebj[q] = gb[static_cast<size_t>(env) * S + r];
       etj[q] = gT[static_cast<size_t>(env) * NS * 6 + (rr / 3) * 6 + half * 3 + rr % 3];
-      wj[q] = P->w_row[r];
+      if constexpr (ENV) wj[q] = env_w_row<D>(P, EP, env, r);
+      else wj[q] = P->w_row[r];
     }
     // A column NV: e = b - t,  t = [T[:,0:3] row-wise ; T[:,3:6] row-wise]  (autogen.py:163-168)
     constexpr int TE = D::JG ? 0 : (S + kWave - 1) / kWave;   // (JG: e enters phase B's fragments)
@@ -427,7 +451,9 @@ __device__ __forceinline__ void setup_env(
     auto ha_row = [&](int r) {
       const double2 x = *reinterpret_cast<const double2*>(sA + r * NAP + i0);
       const double2 y = *reinterpret_cast<const double2*>(sA + r * NAP + j0);
-      const double w = P->w_row[r];
+      double w;
+      if constexpr (ENV) w = sW[r / 3];   // (row r: site r / 3 of [w_pos | w_rot])
+      else w = P->w_row[r];
       const double wx0 = w * x.x, wx1 = w * x.y;
       a00 = fma(wx0, y.x, a00);
       a01 = fma(wx0, y.y, a01);
@@ -939,6 +965,20 @@ __global__ __launch_bounds__(kWave, LEAN ? OSC_SETUP_LEAN_WPS : OSC_SETUP_WPS) v
   __shared__ __attribute__((aligned(16))) double sm[(LEAN && !D::WH) ? D::SMEM_L : D::SMEM];
   setup_env<D, false, LEAN>(P, static_cast<int>(blockIdx.x), nenv, gM, gC, gJ, gb, gT, gmask, ws,
                             sm, gwd);
+}
+
+// The _env entry points' assembly: the same body with the per-env weights (a kernel of its own, so
+// osc_setup_kernel keeps its name, arguments and code).
+template <class D, bool LEAN = false>
+__global__ __launch_bounds__(kWave, LEAN ? OSC_SETUP_LEAN_WPS : OSC_SETUP_WPS) void osc_setup_env_kernel(
+    const DevParams* __restrict__ P, int nenv, const double* __restrict__ gM,
+    const double* __restrict__ gC, const double* __restrict__ gJ, const double* __restrict__ gb,
+    const double* __restrict__ gT, const double* __restrict__ gmask, double* __restrict__ ws,
+    EnvPtrs EP) {
+  // (+ 2 NS site weights where phase B reads them from LDS: Go2 10,240 B, still 16 waves per CU)
+  __shared__ __attribute__((aligned(16))) double sm[(LEAN ? D::SMEM_L : D::SMEM) + (D::JG ? 0 : 2 * D::NS)];
+  setup_env<D, false, LEAN, true>(P, static_cast<int>(blockIdx.x), nenv, gM, gC, gJ, gb, gT, gmask,
+                                  ws, sm, nullptr, nullptr, nullptr, nullptr, EP);
 }
 
 // The fused joint-state tick's assembly (setup_env<D, true>): kinematics from qpos / qvel in the

@@ -53,6 +53,11 @@ MIXED_SYMBOLS = ("osc_batch_tick_multi", "osc_batch_kinematics_pair",
                  "osc_host_feed_create_multi", "osc_host_feed_inputs_part",
                  "osc_host_feed_wait_part")
 
+# include/osc_env_params.h (per-env friction, bounds and task weights), apart likewise;
+# tests/test_env_params_ref.py pins this list to that header's declarations.
+ENV_PARAMS_SYMBOLS = ("osc_batch_solve_env", "osc_batch_solve_warm_env", "osc_batch_assemble_env",
+                      "osc_batch_solve_assembled_env", "osc_batch_solve_assembled_warm_env")
+
 OSC_KIN_MAX_BODIES = 16
 OSC_KIN_MAX_DOFS = 32
 OSC_KIN_MAX_SITES = 32
@@ -92,6 +97,12 @@ class OscModelTuning(ctypes.Structure):
 class OscSolveExtras(ctypes.Structure):
     """osc_solve_extras (include/osc_batch.h): per-call extras of osc_batch_solve_ex."""
     _fields_ = [("wheel_dir", ctypes.c_void_p), ("y", ctypes.c_void_p)]
+
+
+class OscEnvParams(ctypes.Structure):
+    """osc_env_params (include/osc_env_params.h): device arrays, each nullable."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("mu", "u_lb", "u_ub", "fz_lb", "fz_ub", "w_pos",
+                                                "w_rot")]
 
 
 class OscTumblingParams(ctypes.Structure):
@@ -253,6 +264,18 @@ def lib() -> ctypes.CDLL:
     L.osc_batch_solve_ex.restype = ctypes.c_int
     L.osc_batch_assemble_ex.argtypes = [vp, i32] + [vp] * 7 + [vp, ctypes.c_size_t, vp]
     L.osc_batch_assemble_ex.restype = ctypes.c_int
+    ep, xp = ctypes.POINTER(OscEnvParams), ctypes.POINTER(OscSolveExtras)
+    L.osc_batch_solve_env.argtypes = [vp, i32] + [vp] * 6 + [ep, xp] + [vp] * 4 + \
+        [vp, ctypes.c_size_t, vp]
+    L.osc_batch_solve_warm_env.argtypes = [vp, i32] + [vp] * 6 + [ep, xp] + [vp] * 5 + \
+        [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+    L.osc_batch_assemble_env.argtypes = [vp, i32] + [vp] * 6 + [ep, xp] + [vp, ctypes.c_size_t, vp]
+    L.osc_batch_solve_assembled_env.argtypes = [vp, i32, vp, ep, xp] + [vp] * 4 + \
+        [vp, ctypes.c_size_t, vp]
+    L.osc_batch_solve_assembled_warm_env.argtypes = [vp, i32, vp, ep, xp] + [vp] * 5 + \
+        [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+    for name in ENV_PARAMS_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
     L.osc_batch_solve_multi.argtypes = [ctypes.POINTER(OscBatchJob), i32, vp]
     L.osc_batch_solve_multi.restype = ctypes.c_int
     kp = ctypes.POINTER(OscKinDesc)

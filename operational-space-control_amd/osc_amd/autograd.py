@@ -86,7 +86,8 @@ class _OSCSolveData(torch.autograd.Function):
         return None, g["M"], g["C"], g["J"], g["b"], g["T"], None
 
 
-def solve_differentiable(solver: OSCBatchSolver, M, C, J, b, T, mask, data_grads: bool = False):
+def solve_differentiable(solver: OSCBatchSolver, M, C, J, b, T, mask, data_grads: bool = False,
+                         env_params=None):
     """(tau, x, status) of the batch, differentiable with respect to T and b, and with
     data_grads=True with respect to M, C and J as well.
 
@@ -95,7 +96,11 @@ def solve_differentiable(solver: OSCBatchSolver, M, C, J, b, T, mask, data_grads
     data_grads gradients flow to T and b only; M, C, J and mask get None, and M, C or J with
     requires_grad raise ValueError.  M.grad treats all nv^2 entries of M as independent (it is not
     symmetrised).  An env whose status is not 0 contributes zero gradients.  The model must have
-    no wheel rows."""
+    no wheel rows.  env_params (solver.EnvParams) is not supported: the backward kernels read the
+    model's friction and weights."""
+    if env_params is not None:
+        raise NotImplementedError("solve_differentiable: per-env parameters have no backward pass "
+                                  "(the backward kernels read the model's mu and task weights)")
     if not data_grads:
         for name, t in (("M", M), ("C", C), ("J", J)):
             if isinstance(t, torch.Tensor) and t.requires_grad:

@@ -67,7 +67,7 @@ def build(verbose: bool = False, force: bool = False, out: str | None = None,
         [os.path.join(REPO, "include", h) for h in ("osc_batch.h", "osc_producers.h",
                                                      "osc_kinematics.h", "osc_host_feed.h",
                                                      "osc_rollout.h", "osc_mixed.h",
-                                                     "osc_backward.h")] + [__file__]
+                                                     "osc_backward.h", "osc_env_params.h")] + [__file__]
     variant = out != OUT
     if not force and os.path.exists(out):
         t_out = os.path.getmtime(out)

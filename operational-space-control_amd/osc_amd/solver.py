@@ -37,6 +37,55 @@ class SolveResult:
     y: torch.Tensor | None = None           # (nenv, dual_rows) dual solution (OSQP convention)
 
 
+class EnvParams:
+    """Per-env friction, torque and normal-force bounds and task weights (osc_env_params,
+    include/osc_env_params.h), each None (= the model's value for every env) or a float64 torch
+    tensor / numpy array, env-major:
+      mu (nenv,), u_lb / u_ub (nenv, nu), fz_lb / fz_ub (nenv,), w_pos / w_rot (nenv, ns).
+    Shapes and dtypes are checked on the host when a solver takes the block (ValueError before any
+    launch); the values are checked per env on the device, where an invalid env (u_lb >= u_ub, a
+    NaN, a non-finite mu or weight) returns OSC_SOLVE_NUMERICAL and leaves the others untouched."""
+    FIELDS = ("mu", "u_lb", "u_ub", "fz_lb", "fz_ub", "w_pos", "w_rot")
+
+    def __init__(self, mu=None, u_lb=None, u_ub=None, fz_lb=None, fz_ub=None, w_pos=None,
+                 w_rot=None):
+        self.mu, self.u_lb, self.u_ub, self.fz_lb, self.fz_ub = mu, u_lb, u_ub, fz_lb, fz_ub
+        self.w_pos, self.w_rot = w_pos, w_rot
+        for name in self.FIELDS:
+            a = getattr(self, name)
+            if a is None:
+                continue
+            if not isinstance(a, (np.ndarray, torch.Tensor)):
+                raise TypeError(f"EnvParams.{name}: expected torch.Tensor or numpy array")
+            if a.dtype not in (np.float64, torch.float64):
+                raise ValueError(f"EnvParams.{name}: expected float64, got {a.dtype}")
+
+    def shapes(self, nenv: int, dims: dict) -> dict:
+        return dict(mu=(nenv,), u_lb=(nenv, dims["nu"]), u_ub=(nenv, dims["nu"]), fz_lb=(nenv,),
+                    fz_ub=(nenv,), w_pos=(nenv, dims["ns"]), w_rot=(nenv, dims["ns"]))
+
+    def to_device(self, nenv: int, dims: dict, device) -> tuple:
+        """(osc_env_params struct, the device tensors it points to -- keep them alive until the
+        launch is enqueued).  Raises ValueError on a wrong shape, before anything is copied."""
+        want = self.shapes(nenv, dims)
+        for name in self.FIELDS:
+            a = getattr(self, name)
+            if a is not None and tuple(a.shape) != want[name]:
+                raise ValueError(f"EnvParams.{name}: expected shape {want[name]}, got "
+                                 f"{tuple(a.shape)}")
+        c, keep = _lib.OscEnvParams(), []
+        for name in self.FIELDS:
+            a = getattr(self, name)
+            if a is None:
+                continue
+            if isinstance(a, np.ndarray):
+                a = torch.from_numpy(np.ascontiguousarray(a))
+            a = a.to(device=device).contiguous()
+            keep.append(a)
+            setattr(c, name, a.data_ptr())
+        return c, keep
+
+
 class OSCBatchSolver:
     def __init__(self, robot: str, yaml_path: str | None = None, eps_mu: float | None = None,
                  max_iter: int | None = None, device: torch.device | int | None = None,
@@ -126,14 +175,35 @@ class OSCBatchSolver:
         ws = torch.empty((max(nb.value // 8, 2),), dtype=torch.float64, **opts)
         return SolveResult(tau, x, status, iters, ws, y)
 
+    def _env_block(self, env_params, nenv, wheel_dir=None):
+        """(byref(osc_env_params), byref(osc_solve_extras) factory, tensors to keep alive) of an
+        _env call; host-side shape / dtype errors raise here, before any launch."""
+        if not isinstance(env_params, EnvParams):
+            raise TypeError("env_params: expected an EnvParams")
+        if wheel_dir is not None:
+            raise ValueError("env_params: models with wheel rows are not supported")
+        c, keep = env_params.to_device(nenv, self.dims, self.device)
+        return c, keep
+
     def solve_into(self, out: SolveResult, M, C, J, b, T, mask, stream=None,
-                   wheel_dir=None) -> SolveResult:
+                   wheel_dir=None, env_params=None) -> SolveResult:
         """Launch only (no allocation, no host sync): the benchmarked call.  osc_batch_solve, or
-        osc_batch_solve_ex when the model has wheel rows or duals are wanted (out.y)."""
+        osc_batch_solve_ex when the model has wheel rows or duals are wanted (out.y); with
+        env_params (an EnvParams) osc_batch_solve_env."""
         nenv = out.tau.shape[0]
         s = (torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         wsb = ctypes.c_size_t(0 if out.workspace is None else out.workspace.numel() * 8)
+        if env_params is not None:
+            c, keep = self._env_block(env_params, nenv, wheel_dir)
+            ex = _lib.OscSolveExtras(None, out.y.data_ptr() if out.y is not None else None)
+            rc = _lib.lib().osc_batch_solve_env(
+                self._h, nenv, ptr(M), ptr(C), ptr(J), ptr(b), ptr(T), ptr(mask), ctypes.byref(c),
+                ctypes.byref(ex), ptr(out.tau), ptr(out.x), ptr(out.status), ptr(out.iters),
+                ptr(out.workspace), wsb, ctypes.c_void_p(s))
+            if rc != 0:
+                raise _lib.OSCError("osc_batch_solve_env", rc)
+            return out
         if wheel_dir is None and out.y is None:
             rc = _lib.lib().osc_batch_solve(self._h, nenv, ptr(M), ptr(C), ptr(J), ptr(b), ptr(T),
                                             ptr(mask), ptr(out.tau), ptr(out.x), ptr(out.status),
@@ -153,12 +223,21 @@ class OSCBatchSolver:
         return out
 
     def assemble_into(self, out: SolveResult, M, C, J, b, T, mask, stream=None,
-                      wheel_dir=None) -> SolveResult:
-        """First half of solve_into: every env's reduced QP into out.workspace."""
+                      wheel_dir=None, env_params=None) -> SolveResult:
+        """First half of solve_into: every env's reduced QP into out.workspace (env_params: its
+        task weights act here, osc_batch_assemble_env)."""
         nenv = out.tau.shape[0]
         s = (torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         wsb = ctypes.c_size_t(out.workspace.numel() * 8)
+        if env_params is not None:
+            c, keep = self._env_block(env_params, nenv, wheel_dir)
+            rc = _lib.lib().osc_batch_assemble_env(
+                self._h, nenv, ptr(M), ptr(C), ptr(J), ptr(b), ptr(T), ptr(mask), ctypes.byref(c),
+                None, ptr(out.workspace), wsb, ctypes.c_void_p(s))
+            if rc != 0:
+                raise _lib.OSCError("osc_batch_assemble_env", rc)
+            return out
         if wheel_dir is None:
             rc = _lib.lib().osc_batch_assemble(self._h, nenv, ptr(M), ptr(C), ptr(J), ptr(b),
                                                ptr(T), ptr(mask), ptr(out.workspace), wsb,
@@ -171,11 +250,22 @@ class OSCBatchSolver:
             raise _lib.OSCError("osc_batch_assemble", rc)
         return out
 
-    def solve_assembled_into(self, out: SolveResult, mask, stream=None) -> SolveResult:
-        """Second half of solve_into: interior-point solve of the assembled workspace."""
+    def solve_assembled_into(self, out: SolveResult, mask, stream=None,
+                             env_params=None) -> SolveResult:
+        """Second half of solve_into: interior-point solve of the assembled workspace
+        (env_params: its mu and bounds act here, osc_batch_solve_assembled_env)."""
         nenv = out.tau.shape[0]
         s = (torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        if env_params is not None:
+            c, keep = self._env_block(env_params, nenv)
+            rc = _lib.lib().osc_batch_solve_assembled_env(
+                self._h, nenv, ptr(mask), ctypes.byref(c), None, ptr(out.tau), ptr(out.x),
+                ptr(out.status), ptr(out.iters), ptr(out.workspace),
+                ctypes.c_size_t(out.workspace.numel() * 8), ctypes.c_void_p(s))
+            if rc != 0:
+                raise _lib.OSCError("osc_batch_solve_assembled_env", rc)
+            return out
         rc = _lib.lib().osc_batch_solve_assembled(self._h, nenv, ptr(mask), ptr(out.tau),
                                                   ptr(out.x), ptr(out.status), ptr(out.iters),
                                                   ptr(out.workspace),
@@ -239,13 +329,27 @@ class OSCBatchSolver:
         return torch.zeros((max(nb.value // 8, 2),), dtype=torch.float64, device=self.device)
 
     def solve_warm_into(self, out: SolveResult, warm: torch.Tensor, M, C, J, b, T, mask,
-                        stream=None, wheel_dir=None) -> SolveResult:
+                        stream=None, wheel_dir=None, env_params=None) -> SolveResult:
         """osc_batch_solve_warm: as solve_into, starting from (and updating) `warm`, the previous
         tick's solution (the reference's SetWarmStart, operational_space_controller.h:519-526);
-        osc_batch_solve_warm_ex with wheel rows or duals (out.y)."""
+        osc_batch_solve_warm_ex with wheel rows or duals (out.y); with env_params
+        osc_batch_solve_warm_env (the values may change from tick to tick; an env whose set of
+        finite bounds changes needs its valid flag cleared, include/osc_env_params.h)."""
         nenv = out.tau.shape[0]
         s = (torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        if env_params is not None:
+            c, keep = self._env_block(env_params, nenv, wheel_dir)
+            ex = _lib.OscSolveExtras(None, out.y.data_ptr() if out.y is not None else None)
+            rc = _lib.lib().osc_batch_solve_warm_env(
+                self._h, nenv, ptr(M), ptr(C), ptr(J), ptr(b), ptr(T), ptr(mask), ctypes.byref(c),
+                ctypes.byref(ex), ptr(out.tau), ptr(out.x), ptr(out.status), ptr(out.iters),
+                ptr(warm), ctypes.c_size_t(warm.numel() * 8), ptr(out.workspace),
+                ctypes.c_size_t(0 if out.workspace is None else out.workspace.numel() * 8),
+                ctypes.c_void_p(s))
+            if rc != 0:
+                raise _lib.OSCError("osc_batch_solve_warm_env", rc)
+            return out
         if wheel_dir is not None or out.y is not None:
             ex = _lib.OscSolveExtras(wheel_dir.data_ptr() if wheel_dir is not None else None,
                                      out.y.data_ptr() if out.y is not None else None)
@@ -271,10 +375,20 @@ class OSCBatchSolver:
         return out
 
     def solve_assembled_warm_into(self, out: SolveResult, warm: torch.Tensor, mask,
-                                  stream=None) -> SolveResult:
+                                  stream=None, env_params=None) -> SolveResult:
         nenv = out.tau.shape[0]
         s = (torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        if env_params is not None:
+            c, keep = self._env_block(env_params, nenv)
+            rc = _lib.lib().osc_batch_solve_assembled_warm_env(
+                self._h, nenv, ptr(mask), ctypes.byref(c), None, ptr(out.tau), ptr(out.x),
+                ptr(out.status), ptr(out.iters), ptr(warm), ctypes.c_size_t(warm.numel() * 8),
+                ptr(out.workspace), ctypes.c_size_t(out.workspace.numel() * 8),
+                ctypes.c_void_p(s))
+            if rc != 0:
+                raise _lib.OSCError("osc_batch_solve_assembled_warm_env", rc)
+            return out
         rc = _lib.lib().osc_batch_solve_assembled_warm(
             self._h, nenv, ptr(mask), ptr(out.tau), ptr(out.x), ptr(out.status), ptr(out.iters),
             ptr(warm), ctypes.c_size_t(0 if warm is None else warm.numel() * 8),
@@ -295,21 +409,26 @@ class OSCBatchSolver:
                 self._as_dev(mask, (nenv, d["nc"]), "mask"))
 
     def solve(self, M, C, J, b, T, mask, want_x: bool = False, want_y: bool = False,
-              wheel_dir=None) -> SolveResult:
+              wheel_dir=None, env_params=None) -> SolveResult:
         args = self.prepare(M, C, J, b, T, mask)
         nenv = int(args[0].shape[0])
+        if env_params is not None:      # (shape errors: before anything is allocated or launched)
+            self._env_block(env_params, nenv, wheel_dir)
         if wheel_dir is not None:
             wheel_dir = self._as_dev(wheel_dir, (nenv, self.dims["nc"], 6), "wheel_dir")
         out = self.alloc_outputs(nenv, want_x, want_y)
         with torch.cuda.device(self.device):
-            return self.solve_into(out, *args, wheel_dir=wheel_dir)
+            return self.solve_into(out, *args, wheel_dir=wheel_dir, env_params=env_params)
 
 
-def solve_multi_into(jobs, stream=None) -> None:
+def solve_multi_into(jobs, stream=None, env_params=None) -> None:
     """osc_batch_solve_multi: several models' batches in one call on one stream (BASELINE
     configs[4]: Go2 + WaLTER Sr per GPU).  `jobs` = [(solver, SolveResult, (M, C, J, b, T,
     mask)[, wheel_dir]), ...] with device tensors from solver.prepare / solver.alloc_outputs
     (wheel_dir: the wheel-row models' directions, [nenv, nc, 6])."""
+    if env_params is not None:
+        raise NotImplementedError("solve_multi_into: per-env parameters are not supported by the "
+                                  "multi-model call (solve each model with solve_into)")
     arr = (_lib.OscBatchJob * len(jobs))()
     ptr = lambda t: t.data_ptr() if t is not None else None
     dev = None
@@ -370,10 +489,13 @@ def tick_jobs_array(jobs):
     return arr
 
 
-def tick_multi_into(jobs, stream=None) -> None:
+def tick_multi_into(jobs, stream=None, env_params=None) -> None:
     """osc_batch_tick_multi: several models' ticks in one call on one stream -- the mixed-robot
     tick with warm starts and joint-state inputs per job (BASELINE configs[4]).  `jobs` is a list
     of TickJob; each job's results are bitwise those of its single-model call."""
+    if env_params is not None:
+        raise NotImplementedError("tick_multi_into: per-env parameters are not supported by the "
+                                  "mixed-robot tick (solve each model with solve_into)")
     arr = tick_jobs_array(jobs)
     dev = jobs[-1].solver.device if jobs else None
     s = (torch.cuda.current_stream(dev) if stream is None else stream).cuda_stream
