@@ -89,8 +89,10 @@ int osc_batch_solve_backward(const osc_model* model, int32_t nenv, const double*
  * atomics, an env's outputs bitwise independent of its batch; an env whose status is not
  * OSC_SOLVE_OK gets zeros in every output.  Argument rules and return codes as
  * osc_batch_solve_backward (a model with wheel rows is refused; all checks before any launch;
- * nenv == 0 is OSC_OK).  Gradients with respect to the bounds and mu, and backward passes of the
- * warm, joint-state, multi, host-fed and wheel-row entries, remain out of scope. */
+ * nenv == 0 is OSC_OK).  Gradients with respect to the bounds, mu and the site weights, and the
+ * backward pass of a batch solved with per-env parameters (osc_env_params.h):
+ * osc_batch_solve_backward_env, osc_backward_env.h.  Backward passes of the joint-state, multi,
+ * host-fed and wheel-row entries remain out of scope. */
 int osc_batch_solve_backward_data(const osc_model* model, int32_t nenv, const double* M,
                                   const double* J, const double* b, const double* T,
                                   const double* contact_mask, const double* x, const double* y,

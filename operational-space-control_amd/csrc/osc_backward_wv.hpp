@@ -57,13 +57,20 @@ __device__ __forceinline__ BwCol bw_col(int j, const double* sP) {
 // BwLayout block of LDS; wenv, yy, gx, mask: the env's workspace block, duals, dL/dx and contact
 // mask.  On return v = X_y w is whole in every lane and (w0, w1) are the lane's entries of w
 // (columns l and l + 16; the second a mirror of column NY - 1 past NY).
-template <class D>
+// EXT = true (osc_backward_env.hip, the per-env parameter gradients): the pyramid normals take
+// ext->mu, the env's friction, instead of the model's, and ext->r0 / r1 return the lane's entries of
+// r~ = (g_u, g_z) + X_y' g_dv BEFORE the projection.  EXT = false compiles none of it.
+struct BwExt {
+  double mu, r0, r1;
+};
+template <class D, bool EXT = false>
 __device__ __forceinline__ void bw_solve_wv(const DevParams* __restrict__ P, int l, double* B,
                                             const double* __restrict__ wenv,
                                             const double* __restrict__ yy,
                                             const double* __restrict__ gx,
                                             const double* __restrict__ mask,
-                                            double (&v)[D::NV], double& w0, double& w1) {
+                                            double (&v)[D::NV], double& w0, double& w1,
+                                            BwExt* ext = nullptr) {
   constexpr int NV = D::NV, NU = D::NU, NC = D::NC, NY = D::NY, NY1P = D::NY1P;
   constexpr int Y_PYR = NV, Y_U = NV + 4 * NC + NV, Y_Z = Y_U + NU;
   using LY = BwLayout<D>;
@@ -109,7 +116,8 @@ __device__ __forceinline__ void bw_solve_wv(const DevParams* __restrict__ P, int
       q2x = t2 ? ux : q2x, q2y = t2 ? uy : q2y, q2z = t2 ? uz : q2z;
       nq += take ? 1 : 0;
     };
-    const double mu = P->mu;
+    double mu = P->mu;
+    if constexpr (EXT) mu = ext->mu;
     add(1.0, 1.0, -mu, py[0] > 0.0);     // the pyramid rows in Aineq's order
     add(-1.0, 1.0, -mu, py[1] > 0.0);
     add(1.0, -1.0, -mu, py[2] > 0.0);
@@ -199,6 +207,7 @@ __device__ __forceinline__ void bw_solve_wv(const DevParams* __restrict__ P, int
     r0 = fma(X[i * NY1P + j0], g, r0);
     r1 = fma(X[i * NY1P + jj1], g, r1);
   }
+  if constexpr (EXT) ext->r0 = r0, ext->r1 = r1;
   apply_p(r0, r1);
 
   // ---- w = P K^-1 r, refined through the factored form ----

@@ -10,10 +10,10 @@ from . import synth  # noqa: F401
 
 def __getattr__(name):
     # torch-dependent pieces load lazily so CPU-only tooling stays light
-    if name in ("OSCBatchSolver", "SolveResult"):
+    if name in ("OSCBatchSolver", "SolveResult", "EnvParams", "EnvGrads"):
         from . import solver
         return getattr(solver, name)
-    if name == "solve_differentiable":
+    if name in ("solve_differentiable", "solve_differentiable_env"):
         from . import autograd
-        return autograd.solve_differentiable
+        return getattr(autograd, name)
     raise AttributeError(name)

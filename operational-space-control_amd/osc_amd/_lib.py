@@ -57,6 +57,9 @@ MIXED_SYMBOLS = ("osc_batch_tick_multi", "osc_batch_kinematics_pair",
 # tests/test_env_params_ref.py pins this list to that header's declarations.
 ENV_PARAMS_SYMBOLS = ("osc_batch_solve_env", "osc_batch_solve_warm_env", "osc_batch_assemble_env",
                       "osc_batch_solve_assembled_env", "osc_batch_solve_assembled_warm_env")
+# include/osc_backward_env.h (the backward pass with per-env parameters and their gradients), apart
+# likewise; tests/test_backward_env_ref.py pins this list to that header's declarations.
+BACKWARD_ENV_SYMBOLS = ("osc_batch_solve_backward_env",)
 
 OSC_KIN_MAX_BODIES = 16
 OSC_KIN_MAX_DOFS = 32
@@ -101,6 +104,12 @@ class OscSolveExtras(ctypes.Structure):
 
 class OscEnvParams(ctypes.Structure):
     """osc_env_params (include/osc_env_params.h): device arrays, each nullable."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("mu", "u_lb", "u_ub", "fz_lb", "fz_ub", "w_pos",
+                                                "w_rot")]
+
+
+class OscEnvGrads(ctypes.Structure):
+    """osc_env_grads (include/osc_backward_env.h): device output arrays, each nullable."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("mu", "u_lb", "u_ub", "fz_lb", "fz_ub", "w_pos",
                                                 "w_rot")]
 
@@ -319,6 +328,10 @@ def lib() -> ctypes.CDLL:
     L.osc_batch_solve_backward.restype = ctypes.c_int
     L.osc_batch_solve_backward_data.argtypes = [vp, i32] + [vp] * 16 + [ctypes.c_size_t, vp]
     L.osc_batch_solve_backward_data.restype = ctypes.c_int
+    L.osc_batch_solve_backward_env.argtypes = [vp, i32] + [vp] * 5 + \
+        [ctypes.POINTER(OscEnvParams)] + [vp] * 10 + [ctypes.POINTER(OscEnvGrads), vp,
+                                                     ctypes.c_size_t, vp]
+    L.osc_batch_solve_backward_env.restype = ctypes.c_int
     L.osc_host_feed_create.argtypes = [vp, vp, i32, i32, ctypes.c_uint32, i32, ctypes.POINTER(vp)]
     L.osc_host_feed_create.restype = ctypes.c_int
     L.osc_host_feed_destroy.argtypes = [vp]

@@ -14,12 +14,18 @@ with data_grads=True, filling only the gradients autograd asks for.  By default 
 T and b ONLY: M, C, J and mask get None (a None is not a zero), so M, C or J with requires_grad
 raise instead of silently training nothing.  The mask never gets a gradient; the task weights are
 model constants, not tensors (their gradient: OSCBatchSolver.backward_data_into's grad_wrow).
+
+With per-env parameters (solver.EnvParams; include/osc_backward_env.h):
+
+    p = EnvParams(mu=mu, fz_ub=cap, w_pos=w)     # tensors with requires_grad get a gradient
+    tau, x, status = solve_differentiable_env(solver, M, C, J, b, T, mask, p)
+    loss(tau, x).backward()        # mu.grad, cap.grad, w.grad, T.grad, b.grad
 """
 from __future__ import annotations
 
 import torch
 
-from .solver import OSCBatchSolver
+from .solver import EnvGrads, EnvParams, OSCBatchSolver
 
 
 class _OSCSolve(torch.autograd.Function):
@@ -96,11 +102,12 @@ def solve_differentiable(solver: OSCBatchSolver, M, C, J, b, T, mask, data_grads
     data_grads gradients flow to T and b only; M, C, J and mask get None, and M, C or J with
     requires_grad raise ValueError.  M.grad treats all nv^2 entries of M as independent (it is not
     symmetrised).  An env whose status is not 0 contributes zero gradients.  The model must have
-    no wheel rows.  env_params (solver.EnvParams) is not supported: the backward kernels read the
-    model's friction and weights."""
+    no wheel rows.  env_params (solver.EnvParams) is not supported here -- this function's backward
+    kernels read the model's friction and weights: solve_differentiable_env takes it."""
     if env_params is not None:
         raise NotImplementedError("solve_differentiable: per-env parameters have no backward pass "
-                                  "(the backward kernels read the model's mu and task weights)")
+                                  "(the backward kernels read the model's mu and task weights); "
+                                  "use solve_differentiable_env")
     if not data_grads:
         for name, t in (("M", M), ("C", C), ("J", J)):
             if isinstance(t, torch.Tensor) and t.requires_grad:
@@ -109,5 +116,79 @@ def solve_differentiable(solver: OSCBatchSolver, M, C, J, b, T, mask, data_grads
     M, C, J, b, T, mask = solver.prepare(M, C, J, b, T, mask)
     fn = _OSCSolveData if data_grads else _OSCSolve
     x, status = fn.apply(solver, M, C, J, b, T, mask)
+    d = solver.dims
+    return x[:, d["nv"]:d["nv"] + d["nu"]], x, status
+
+
+class _OSCSolveEnv(torch.autograd.Function):
+    """The solve with per-env parameters; the seven EnvParams fields follow the data inputs as
+    explicit inputs (a tensor, or None for a field that is absent or a numpy array)."""
+
+    @staticmethod
+    def forward(ctx, solver, env_params, M, C, J, b, T, mask, *fields):
+        nenv = int(M.shape[0])
+        out = solver.alloc_outputs(nenv, want_x=True, want_y=True)
+        with torch.cuda.device(solver.device):
+            solver.solve_into(out, M, C, J, b, T, mask, env_params=env_params)
+        ctx.solver, ctx.out, ctx.env_params = solver, out, env_params
+        ctx.save_for_backward(M, J, b, T, mask)
+        ctx.mark_non_differentiable(out.status)
+        return out.x, out.status
+
+    @staticmethod
+    def backward(ctx, grad_x, _grad_status):
+        solver, out = ctx.solver, ctx.out
+        M, J, b, T, mask = ctx.saved_tensors
+        d = solver.dims
+        nenv = out.tau.shape[0]
+        need = dict(zip(("M", "C", "J", "b", "T"), ctx.needs_input_grad[2:7]))
+        need_p = dict(zip(EnvParams.FIELDS, ctx.needs_input_grad[8:15]))
+        if grad_x is None or not (any(need.values()) or any(need_p.values())):
+            return (None,) * 15
+        grad_x = grad_x.to(dtype=torch.float64).contiguous()
+        shape = dict(M=(nenv, d["nv"], d["nv"]), C=(nenv, d["nv"]), J=(nenv, d["s"], d["nv"]),
+                     b=(nenv, d["s"]), T=(nenv, d["ns"], 6))
+        g = {k: (torch.empty(shape[k], dtype=torch.float64, device=solver.device) if need[k]
+                 else None) for k in shape}
+        eg = EnvGrads.empty(nenv, d, solver.device, [k for k in EnvParams.FIELDS if need_p[k]])
+        with torch.cuda.device(solver.device):
+            solver.backward_env_into(out, M, J, b, T, mask, grad_x, env_params=ctx.env_params,
+                                     grad_M=g["M"], grad_C=g["C"], grad_J=g["J"], grad_T=g["T"],
+                                     grad_b=g["b"], env_grads=eg)
+        return (None, None, g["M"], g["C"], g["J"], g["b"], g["T"], None,
+                *(getattr(eg, k) for k in EnvParams.FIELDS))
+
+
+def solve_differentiable_env(solver: OSCBatchSolver, M, C, J, b, T, mask, env_params: EnvParams,
+                             data_grads: bool = False):
+    """(tau, x, status) of the batch solved with per-env parameters (solver.EnvParams),
+    differentiable with respect to those parameters, to T and b, and with data_grads=True to M, C
+    and J as well.
+
+    An EnvParams field that is a torch tensor with requires_grad -- float64, on the solver's
+    device, ValueError otherwise -- receives a gradient; a numpy field, or a tensor without
+    requires_grad, gets none (its .grad stays None).  One backward launch
+    (osc_batch_solve_backward_env) fills only what autograd asks for.  The gradient with respect to
+    fz_lb at a contact resting on the pyramid's apex (fz_lb x mask = 0) is the left derivative, 0
+    (include/osc_backward_env.h).  Everything else as solve_differentiable."""
+    if not isinstance(env_params, EnvParams):
+        raise TypeError("solve_differentiable_env: env_params must be an EnvParams")
+    if not data_grads:
+        for name, t in (("M", M), ("C", C), ("J", J)):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise ValueError(f"solve_differentiable_env: no gradient with respect to {name} "
+                                 "(pass data_grads=True)")
+    M, C, J, b, T, mask = solver.prepare(M, C, J, b, T, mask)
+    fields = []
+    for name in EnvParams.FIELDS:
+        a = getattr(env_params, name)
+        if isinstance(a, torch.Tensor) and a.requires_grad:
+            if a.device != solver.device:
+                raise ValueError(f"solve_differentiable_env: EnvParams.{name} requires a gradient "
+                                 f"and must be on {solver.device}")
+            fields.append(a)
+        else:
+            fields.append(None)
+    x, status = _OSCSolveEnv.apply(solver, env_params, M, C, J, b, T, mask, *fields)
     d = solver.dims
     return x[:, d["nv"]:d["nv"] + d["nu"]], x, status

@@ -86,6 +86,48 @@ class EnvParams:
         return c, keep
 
 
+class EnvGrads:
+    """Gradients of a loss with respect to the per-env parameters (osc_env_grads,
+    include/osc_backward_env.h): the mirror of EnvParams for outputs.  Each field is None (= not
+    computed) or a contiguous float64 torch tensor on the solver's device, shaped as EnvParams';
+    OSCBatchSolver.backward_env_into fills them.  Shape, dtype, device and layout are checked on
+    the host when a solver takes the block (ValueError before any launch)."""
+    FIELDS = EnvParams.FIELDS
+
+    def __init__(self, mu=None, u_lb=None, u_ub=None, fz_lb=None, fz_ub=None, w_pos=None,
+                 w_rot=None):
+        self.mu, self.u_lb, self.u_ub, self.fz_lb, self.fz_ub = mu, u_lb, u_ub, fz_lb, fz_ub
+        self.w_pos, self.w_rot = w_pos, w_rot
+        for name in self.FIELDS:
+            a = getattr(self, name)
+            if a is not None and not isinstance(a, torch.Tensor):
+                raise TypeError(f"EnvGrads.{name}: expected torch.Tensor")
+
+    @classmethod
+    def empty(cls, nenv: int, dims: dict, device, fields=None) -> "EnvGrads":
+        """Uninitialised tensors for `fields` (default: all seven)."""
+        sh = EnvParams().shapes(nenv, dims)
+        return cls(**{k: torch.empty(sh[k], dtype=torch.float64, device=device)
+                      for k in (cls.FIELDS if fields is None else fields)})
+
+    def to_struct(self, nenv: int, dims: dict, device) -> "_lib.OscEnvGrads":
+        want = EnvParams().shapes(nenv, dims)
+        c = _lib.OscEnvGrads()
+        for name in self.FIELDS:
+            a = getattr(self, name)
+            if a is None:
+                continue
+            if a.dtype != torch.float64:
+                raise ValueError(f"EnvGrads.{name}: expected float64, got {a.dtype}")
+            if tuple(a.shape) != want[name]:
+                raise ValueError(f"EnvGrads.{name}: expected shape {want[name]}, got "
+                                 f"{tuple(a.shape)}")
+            if a.device != torch.device(device) or not a.is_contiguous():
+                raise ValueError(f"EnvGrads.{name}: expected a contiguous tensor on {device}")
+            setattr(c, name, a.data_ptr())
+        return c
+
+
 class OSCBatchSolver:
     def __init__(self, robot: str, yaml_path: str | None = None, eps_mu: float | None = None,
                  max_iter: int | None = None, device: torch.device | int | None = None,
@@ -319,6 +361,38 @@ class OSCBatchSolver:
             ctypes.c_size_t(out.workspace.numel() * 8), ctypes.c_void_p(s))
         if rc != 0:
             raise _lib.OSCError("osc_batch_solve_backward_data", rc)
+
+    def backward_env_into(self, out: SolveResult, M, J, b, T, mask, grad_x, env_params=None,
+                          grad_M=None, grad_C=None, grad_J=None, grad_wrow=None, grad_T=None,
+                          grad_b=None, env_grads=None, stream=None) -> None:
+        """Launch only: osc_batch_solve_backward_env (include/osc_backward_env.h).  As
+        backward_data_into after a forward solve_into / solve_warm_into with env_params (the same
+        EnvParams block; None after a forward call without one), and the gradients of the per-env
+        parameters into env_grads (an EnvGrads; each field None or a tensor).  A None output is
+        not computed; with only mu / bound gradients asked for, the solve with M and the pass over
+        J are skipped.  An env whose status is not 0 gets zeros."""
+        if out.x is None or out.y is None or out.workspace is None:
+            raise ValueError("backward_env_into needs the forward solve's design vector, duals "
+                             "and workspace (alloc_outputs(want_x=True, want_y=True))")
+        nenv = out.tau.shape[0]
+        keep, cp, cg = None, None, None
+        if env_params is not None:
+            c, keep = self._env_block(env_params, nenv)
+            cp = ctypes.byref(c)
+        if env_grads is not None:
+            if not isinstance(env_grads, EnvGrads):
+                raise TypeError("env_grads: expected an EnvGrads")
+            g = env_grads.to_struct(nenv, self.dims, self.device)
+            cg = ctypes.byref(g)
+        s = (torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = _lib.lib().osc_batch_solve_backward_env(
+            self._h, nenv, ptr(M), ptr(J), ptr(b), ptr(T), ptr(mask), cp, ptr(out.x), ptr(out.y),
+            ptr(out.status), ptr(grad_x), ptr(grad_M), ptr(grad_C), ptr(grad_J), ptr(grad_wrow),
+            ptr(grad_T), ptr(grad_b), cg, ptr(out.workspace),
+            ctypes.c_size_t(out.workspace.numel() * 8), ctypes.c_void_p(s))
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_solve_backward_env", rc)
 
     def alloc_warm_state(self, nenv: int) -> torch.Tensor:
         """Zero-filled warm state (osc_warm_state_bytes): every env starts cold on its first tick."""
