@@ -94,7 +94,8 @@ constexpr int even(int a) { return (a + 1) & ~1; }   // keep LDS/workspace regio
 // [Hr | g] = X'T1 always (T1 stays in registers), Ha = 2 [J e]'W[J e] where [J e] fits one
 // 16-column tile (WaLTER, NA = 15); Go2's 19 columns would pad to 32 and stay on exact 2x2 VALU
 // tiles (Go2 4,096: phase B 7.7k vs 3.5k clocks per wave).  X, H_dv, f_dv and [Hr | g] are stored
-// to the workspace where they are formed (no copy-out phase).
+// to the workspace where they are formed (no copy-out phase) -- but for Go2's lean assembly, which
+// forms them in LDS and copies the block out at the end of the wave (SMEM_L below).
 // WH_: the model carries the wheel no-slip equality rows (two per contact wheel).
 template <int NV_, int NU_, int NC_, int NS_, bool WH_ = false>
 struct Dims {
@@ -203,7 +204,19 @@ struct Dims {
   static constexpr int O_HD_L = R1 + R2;
   static constexpr int O_MASK_L = O_HD_L + even(NV * NV);
   static constexpr int SMEM_L = O_MASK_L + even(NC);
+  // Lean assembly, the hand-off (round 10): nothing goes to the workspace where it is formed.
+  // f_dv is parked behind X in A's last rows (task rows phase C does not read, written once
+  // phase B has read them) and [g | Hr] is staged, in the workspace's own layout, over what is
+  // left of A, M and C (dead by phase D); the wave's last act copies [g | Hr], X, H_dv and f_dv
+  // out as one block of 16-byte stores (osc_setup.hpp: the hand-off).
+  static constexpr int O_FD_L = NV * NY1P;
+  static constexpr int O_GH_L = O_FD_L + even(NV);
   static_assert(NV * NY1P <= R1 + R2, "lean assembly: X over A and M");
+  static_assert(JG || WH || (O_FD_L >= 3 * NS * NAP && O_GH_L <= R1),
+                "lean assembly: f_dv in A's rotational rows, clear of the contact rows and of M");
+  static_assert(JG || WH || O_GH_L + W_X <= O_HD_L, "lean assembly: [g | Hr] staged below H_dv");
+  static_assert(W_X % 2 == 0 && W_HD % 2 == 0 && W_GD % 2 == 0 && W_SOL % 2 == 0 &&
+                O_FD_L % 2 == 0 && O_HD_L % 2 == 0, "the hand-off moves 16-byte pieces");
   static_assert(NW <= kRow, "IPM: one wheel row per lane of the env's row");
   static_assert(NV % 2 == 0, "setup: J rows are staged in 16-byte chunks");
   static_assert(SMEM * 8 <= 64 * 1024, "setup LDS budget per env");
@@ -583,6 +596,18 @@ __device__ __forceinline__ void upper_pair(int p, int& i, int& j) {
   r = (r > 0 && start(r) > p) ? r - 1 : r;
   i = r;
   j = p - start(r) + r;
+}
+
+// The same pair by counting the rows that start at or before p: N - 1 compare-and-add steps on
+// compile-time constants, no square root and no quarter-rate multiply but one 24-bit one (the
+// lean assembly, where every issued instruction counts: DESIGN.md §10 #2).
+template <int N>
+__device__ __forceinline__ void upper_pair_cmp(int p, int& i, int& j) {
+  int r = 0;
+#pragma unroll
+  for (int k = 1; k < N; ++k) r += (p >= k * (2 * N - k + 1) / 2) ? 1 : 0;
+  i = r;
+  j = p - (__mul24(r, 2 * N + 1 - r) >> 1) + r;
 }
 
 // c += bcast_K(src) * m  in ONE instruction: v_fmac_f64_dpp with row_newbcast:K (the DPP

@@ -112,7 +112,10 @@ __device__ __noinline__ void wave_mgs_lds(double* rows, int lane, double drop, d
 // 10.2 instead of 14.2 KB of LDS, so 16 waves fit a CU.  Round 5 adopted the unroll for batches
 // past one round of interior-point waves only (4,096: 0.1646 vs 0.1620 ms, when LDS still capped
 // a CU at 11 waves; profiles/r05/ab_setup_unroll4.jsonl); with the LDS cut it wins at every size
-// (profiles/r06/lean_lds/).
+// (profiles/r06/lean_lds/).  Round 10: that variant (kHaG) keeps X, H_dv, f_dv and [Hr | g] in
+// LDS until the wave's last act, the hand-off, copies the env's block to the workspace in
+// write-through 16-byte stores; and its phases take the forms that issue the fewest instructions
+// (the `if constexpr (kHaG)` arms: same arithmetic, bitwise the same block).
 // ENV = true (the _env entry points, include/osc_env_params.h; QP-input form only): the task-row
 // weights are the env's own -- row r of site k takes EP.w_pos[env][k] (translational half) or
 // EP.w_rot[env][k], a NULL array the model's w_row -- and a non-finite one becomes NaN, so that the
@@ -124,6 +127,11 @@ __device__ __forceinline__ double env_w_row(const DevParams* __restrict__ P, con
   const double w = a ? a[static_cast<size_t>(env) * D::NS + (r % (3 * D::NS)) / 3] : P->w_row[r];
   return isfinite(w) ? w : __builtin_nan("");
 }
+// (The lean assembly's hand-off stores are write-through; -DOSC_SETUP_WT=0 for A/B builds: plain
+// stores, Go2 4,096 assembly 24.5 -> 26.4 us, profiles/r10/setup_handoff/.)
+#ifndef OSC_SETUP_WT
+#define OSC_SETUP_WT 1
+#endif
 template <class D, bool KIN = false, bool LEAN = false, bool ENV = false>
 __device__ __forceinline__ void setup_env(
     const DevParams* __restrict__ P, int env, int nenv, const double* __restrict__ gM,
@@ -366,21 +374,16 @@ __device__ __forceinline__ void setup_env(
   // H_dv = 2 J'WJ + 2 w_reg I,  f_dv = 2 J'W (b - t)   (autogen.py:131-238, 304-319)
   // One 2x2 tile of the upper triangle per lane (column pairs read as one 16-byte LDS load);
   // each entry (i <= j) accumulates fma(w_r A_ri, A_rj) over r in order.
-  // (H_dv and f_dv also go to the workspace from here, no write phase)
+  // (H_dv and f_dv also go to the workspace from here, no write phase -- kHaG: to LDS alone, by
+  // the tile loop's own stores below; the hand-off at the end of the wave copies them out)
   double* const wha = ws + static_cast<size_t>(env) * D::WS;
+  double* const sFd = sm + D::O_FD_L;   // kHaG: f_dv, over rows of A that only phase B reads
   auto put_ha = [&](int i, int j, double v) {
     if (i >= NA || j >= NA) return;
     v *= 2.0;
     if (i == j && i < NV) v += 2.0 * P->w_reg;
-    if constexpr (kHaG) {   // H_dv alone, row stride NV
-      if (j < NV) {
-        sHa[i * NV + j] = v;
-        sHa[j * NV + i] = v;
-      }
-    } else {
-      sHa[i * NA + j] = v;
-      sHa[j * NA + i] = v;
-    }
+    sHa[i * NA + j] = v;
+    sHa[j * NA + i] = v;
     if (j < NV) {                          // H_dv (i <= j < NV), both triangles
       wha[D::W_HD + i * NV + j] = v;
       wha[D::W_HD + j * NV + i] = v;
@@ -441,7 +444,8 @@ __device__ __forceinline__ void setup_env(
   } else
   for (int p = lane; p < D::NBA; p += kWave) {
     int i0, j0;
-    upper_pair<D::NA2>(p, i0, j0);
+    if constexpr (kHaG) upper_pair_cmp<D::NA2>(p, i0, j0);
+    else upper_pair<D::NA2>(p, i0, j0);
     i0 *= 2;
     j0 *= 2;
     double a00 = 0.0, a01 = 0.0, a10 = 0.0, a11 = 0.0;
@@ -466,10 +470,42 @@ __device__ __forceinline__ void setup_env(
     } else {
       for (int r = 0; r < S; ++r) ha_row(r);   // (fully unrolled by the compiler)
     }
-    put_ha(i0, j0, a00);
-    put_ha(i0, j0 + 1, a01);
-    if (i0 != j0) put_ha(i0 + 1, j0, a10);   // diagonal tile: (i0+1, i0) mirrors a01
-    put_ha(i0 + 1, j0 + 1, a11);
+    if constexpr (kHaG) {
+      // H_dv alone (row stride NV) and f_dv to LDS, no branch per entry: a lane's tile is an H_dv
+      // tile (j0 < NV: four entries, both triangles -- on a diagonal tile a01 serves (i0+1, i0)
+      // too, as put_ha's callers have it), an f_dv tile (j0 = NV: a00 and a10 are f_dv[i0],
+      // f_dv[i0+1]) or the corner (nothing); the stores of the kinds it is not go to a dump row.
+      // The values are put_ha's: 2 a, + 2 w_reg on H_dv's diagonal (2 w_reg is exact, so the
+      // sum rounds as the fused form does).
+      static_assert(D::NBA <= kWave, "lean assembly: one tile per lane, one trip");
+      static_assert(NA == NV + 1 && NAP == NV + 2 && D::O_GH_L + NV + 2 <= D::R1,
+                    "f_dv is the last column pair; the dump row lies in A's dead rows");
+      wave_sync();   // every tile's reads of A are issued: f_dv may overwrite its rows
+      constexpr int DUMP = D::O_GH_L;
+      const bool dg = i0 == j0, hd = j0 < NV;
+      const double wd = 2.0 * P->w_reg;
+      const double v00 = a00 * 2.0, v11 = a11 * 2.0;
+      const double d00 = dg ? v00 + wd : v00, d11 = dg ? v11 + wd : v11;
+      const double v01 = a01 * 2.0, v10 = (dg ? a01 : a10) * 2.0;
+      const int pi = hd ? D::O_HD_L + __mul24(i0, NV) + j0 : DUMP;
+      const int qi = hd ? D::O_HD_L + __mul24(j0, NV) + i0 : DUMP;
+      const int fi = (!hd && !dg) ? D::O_FD_L + i0 : DUMP;
+      sm[pi] = d00;
+      sm[pi + 1] = v01;
+      sm[pi + NV] = v10;
+      sm[pi + NV + 1] = d11;
+      sm[qi] = d00;
+      sm[qi + NV] = v01;
+      sm[qi + 1] = v10;
+      sm[qi + NV + 1] = d11;
+      sm[fi] = v00;
+      sm[fi + 1] = v10;
+    } else {
+      put_ha(i0, j0, a00);
+      put_ha(i0, j0 + 1, a01);
+      if (i0 != j0) put_ha(i0 + 1, j0, a10);   // diagonal tile: (i0+1, i0) mirrors a01
+      put_ha(i0 + 1, j0 + 1, a11);
+    }
   }
 
   STAMP_END(1);
@@ -507,7 +543,13 @@ __device__ __forceinline__ void setup_env(
         cu ? sM + NB * NV + NB + c : (cz ? sA + (JC0 - JR0 + c - NU) * NAP + NB : sC + NB);
     const double usg = cz ? -1.0 : 1.0;
 #pragma unroll
-    for (int i = 0; i < NB; ++i) x[i] = pinned ? 0.0 : xsg * xp[i * xs];
+    for (int i = 0; i < NB; ++i) {
+      // (kHaG: the reads first, on every lane -- a pinned lane's pointer is as valid -- then the
+      // selects; left alone each read sinks into its own exec-masked arm and waits there)
+      double t = xp[i * xs];
+      if constexpr (kHaG) in_vgpr(t);
+      x[i] = pinned ? 0.0 : xsg * t;
+    }
     // LDL^T of the NB x NB base block (redundantly per lane; NB^3/6 flops)
     double L[NB][NB];
     double dinv[NB];
@@ -547,7 +589,9 @@ __device__ __forceinline__ void setup_env(
     for (int t = 0; t < kUStep; ++t) {
       const int a = a_lo + t;
       if (a < NU) {
-        double acc = pinned ? 0.0 : usg * up[a * xs];
+        double u0 = up[a * xs];
+        if constexpr (kHaG) in_vgpr(u0);
+        double acc = pinned ? 0.0 : usg * u0;
 #pragma unroll
         for (int i = 0; i < NB; ++i) acc = fma(sM[(NB + a) * NV + i], x[i], acc);
         if constexpr (kHaG) uacc[t] = acc;
@@ -589,11 +633,15 @@ __device__ __forceinline__ void setup_env(
 #pragma unroll
     for (int i = 0; i < NU; ++i) col[i] = sU[i * NY1P + (lj < NU ? lj : 0)];
     double dj = 1.0;
+    double dinv[NU];
     static_for<0, NU>([&](auto K) {
       constexpr int k = decltype(K)::value;
       const double pk = bcast_guarded<k>(col[k]);
       const double rk = pk > 0.0 ? recip1(pk) : __builtin_nan("");   // 1 / S_k[k][k] (M SPD)
-      if (lj == k) dj = rk;
+      // (kHaG: pk is the row's lane k on every lane, so rk already is what broadcasting dj from
+      // lane k gives below -- kept as it is formed, no select and no second broadcast)
+      if constexpr (kHaG) dinv[k] = rk;
+      else if (lj == k) dj = rk;
       const double m = (lj > k) ? -col[k] * rk : 0.0;          // -S_k[k][j] / d_k, lanes j > k
       static_for<k + 1, NU>([&](auto I) {
         constexpr int i = decltype(I)::value;
@@ -601,11 +649,13 @@ __device__ __forceinline__ void setup_env(
       });
     });
     // lane j: col[i > j] = L[i][j] d_j (unscaled column), dj = 1 / d_j
-    double dinv[NU];
-    static_for<0, NU>([&](auto K) {
-      constexpr int k = decltype(K)::value;
-      dinv[k] = bcast_guarded<k>(dj);
-    });
+    if constexpr (!kHaG) {
+      static_for<0, NU>([&](auto K) {
+        constexpr int k = decltype(K)::value;
+        dinv[k] = bcast_guarded<k>(dj);
+      });
+    }
+    (void)dj;
     STAMP_END(6);
     STAMP_BEGIN();
     const int c = lane;
@@ -614,7 +664,10 @@ __device__ __forceinline__ void setup_env(
     double xa[NU], xb[NB], xbc[NB];
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
-      const double u = sU[i * NY1P + cc];
+      double u = sU[i * NY1P + cc];
+      // (kHaG: read on every lane, ahead of the select -- left alone the load sinks into an
+      // exec-masked arm per i, each with its own LDS wait)
+      if constexpr (kHaG) in_vgpr(u);
       xa[i] = cu ? ((i == c) ? 1.0 : 0.0) : -u;
     }
 #pragma unroll
@@ -654,19 +707,32 @@ __device__ __forceinline__ void setup_env(
       for (int r = 0; r < NB; ++r) fmac_bcast<q>(xb[r], xbc[r], xa[q]);
     });
     wave_sync();   // every lane has read X_b and U before any column is overwritten
-    if (c < NY1P) {
-      double* const wx = ws + static_cast<size_t>(env) * D::WS + D::W_X;   // X: also to the workspace
+    if constexpr (kHaG) {
+      // X to LDS alone (the hand-off at the end of the wave copies it out): the live columns as
+      // they are, and the padding column's zeros from lanes that hold no column, one row each --
+      // no select per entry
+      static_assert(NY1P - NY1 <= 1 && NY1P + NV <= kWave, "one padding column, a lane per row");
+      if (live) {
+#pragma unroll
+        for (int r = 0; r < NB; ++r) sX[r * NY1P + c] = xb[r];
+#pragma unroll
+        for (int i = 0; i < NU; ++i) sX[(NB + i) * NY1P + c] = xa[i];
+      }
+      if (NY1P > NY1 && c >= NY1P && c < NY1P + NV) sX[(c - NY1P) * NY1P + NY1] = 0.0;
+    } else if (c < NY1P) {
+      // X: also to the workspace
+      double* const wx = ws + static_cast<size_t>(env) * D::WS + D::W_X;
 #pragma unroll
       for (int r = 0; r < NB; ++r) {
         const double v = live ? xb[r] : 0.0;
         sX[r * NY1P + c] = v;
-        wx[r * NY1P + c] = v;
+        if constexpr (!kHaG) wx[r * NY1P + c] = v;
       }
 #pragma unroll
       for (int i = 0; i < NU; ++i) {
         const double v = live ? xa[i] : 0.0;
         sX[(NB + i) * NY1P + c] = v;
-        wx[(NB + i) * NY1P + c] = v;
+        if constexpr (!kHaG) wx[(NB + i) * NY1P + c] = v;
       }
     }
     wave_sync();
@@ -819,9 +885,7 @@ __device__ __forceinline__ void setup_env(
   STAMP_END(2);
   STAMP_BEGIN();
   // ---------------- Phase D: reduced Hessian / gradient ----------------------------------
-  // (kHaG: f_dv comes back from the workspace -- this wavefront's own stores of phase B, complete
-  // and visible to its loads after a workgroup-scope fence)
-  if constexpr (kHaG) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  // (kHaG: f_dv comes back from where phase B parked it in LDS)
   // Hr = X' T1 + 2 (w_tau + w_reg) I_u + 2 w_reg I_z,  g = last column,  T1 = H_dv X (+ f_dv in
   // the affine column).
   {
@@ -859,7 +923,7 @@ __device__ __forceinline__ void setup_env(
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
           const int row = 16 * rb + lg + 4 * rr, col = 16 * cb + lc;
-          const double f = kHaG ? wha[D::W_GD + (row < NV ? row : 0)]
+          const double f = kHaG ? sFd[row < NV ? row : 0]
                                 : sHa[(row < NV ? row : 0) * NA + NV];
           t1[rb][cb][rr] = (row < NV && col == NY) ? f : 0.0;
         }
@@ -872,7 +936,9 @@ __device__ __forceinline__ void setup_env(
           t1[rb][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(hf[rb][q], xf[q][cb], t1[rb][cb], 0, 0, 0);
     const double wu2 = 2.0 * (P->w_torque + P->w_reg);
     const double wr2 = 2.0 * P->w_reg;
-    double* wsv = ws + static_cast<size_t>(env) * D::WS;   // [Hr | g] out from registers
+    // [Hr | g] out from registers (kHaG: into their LDS staging block, laid out as the workspace's
+    // first W_X doubles)
+    double* wsv = kHaG ? sm + D::O_GH_L : ws + static_cast<size_t>(env) * D::WS;
     // Hr[a][b] = Hr[b][a] = v (a <= b) in the workspace's Hr layout (hr_off: compact without wheel
     // rows -- rows 16.. whole, the leading 16 x 16 block as a packed triangle)
     auto store_hr = [&](int a, int b, double v) {
@@ -900,9 +966,69 @@ __device__ __forceinline__ void setup_env(
           hacc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(xf[q][ab], t1[q / 4][bb][q % 4], hacc[t],
                                                          0, 0, 0);
     }
+    if constexpr (kHaG) {
+      // [Hr | g] into the staging block, every case of the layout resolved per tile at compile
+      // time (ab, bb and the register rr are constants; the lane adds lg = a's offset in the tile
+      // and lc = b's):
+      //   b >= 16: row b of A (b < NY) or g (b = NY), one base per lane and tile, + a;
+      //            and, a >= 16 and a < b, row a of A too;
+      //   b < 16:  the packed triangle, offset b + a (31 - a) / 2 -- with a = lg + 4 rr that is
+      //            lg (31 - lg) / 2 + rr (62 - 4 lg) - 8 rr^2, so one multiply per lane.
+      // An element that is not stored (a > b, b > NY, the corner) goes to a dump row behind the
+      // block instead of around an exec-mask branch.  The arithmetic on v is the general path's.
+      static_assert(D::HRC && !D::WH && kRow == 16 && NY - NU <= 32, "compact Hr, no rotation");
+      static_assert(D::O_GH_L + D::W_X + 16 * CB <= D::O_HD_L, "the dump row fits below H_dv");
+      double* const sG = sm + D::O_GH_L;
+      constexpr int DUMP = D::W_X;
+      const int l3 = lg & 3;   // (= lg: tells the compiler its range)
+      const int tri0 = D::W_HR + D::HR_T + (__mul24(l3, 31 - l3) >> 1) + lc, tris = 62 - 4 * l3;
+      static_for<0, CB>([&](auto AB) {
+        constexpr int ab = decltype(AB)::value;
+        static_for<ab, CB>([&](auto BB) {
+          constexpr int bb = decltype(BB)::value;
+          constexpr int tile = ab * CB - ab * (ab - 1) / 2 + (bb - ab);
+          const d4 h = hacc[tile];
+          const int b = 16 * bb + lc;
+          // row b of A, g, or the dump row (bb >= 1)
+          const int base_b = b < NY ? D::W_HR + (b - kRow) * NY : (b == NY ? D::W_G : DUMP);
+          static_for<0, 4>([&](auto RR) {
+            constexpr int rr = decltype(RR)::value;
+            constexpr int amin = 16 * ab + 4 * rr, amax = amin + 3;
+            if constexpr (amin < NY) {   // (a >= NY: nothing to store -- a <= b <= NY, no corner)
+              const int a = amin + l3;
+              double v = h[rr];
+              if constexpr (ab == bb) {   // the diagonal's weights
+                double vd;
+                const double vu = v + wu2;
+                if constexpr (amin >= NU) {
+                  const int kz = __mul24(a - NU, 11) >> 5;   // (a - NU) / 3 below 32
+                  const double mk = sMask[(amax < NY || kz < NC) ? kz : NC - 1];
+                  vd = (mk == 0.0) ? 1.0 : v + wr2;   // pinned z: identity row
+                } else if constexpr (amax < NU) {
+                  vd = vu;
+                } else {
+                  const int kz = a >= NU ? __mul24(a - NU, 11) >> 5 : 0;
+                  const double mk = sMask[kz];
+                  vd = a < NU ? vu : ((mk == 0.0) ? 1.0 : v + wr2);
+                }
+                v = (a == b) ? vd : v;
+              }
+              const bool in = (ab < bb || a <= b) && (amax < NY || a < NY);
+              if constexpr (bb == 0) {
+                sG[in ? tri0 + rr * tris - 8 * rr * rr : DUMP + a] = v;
+              } else {
+                sG[(in ? base_b : DUMP) + a] = v;
+                if constexpr (ab >= 1)
+                  sG[(a < b && b < NY) ? D::W_HR + (a - kRow) * NY + b : DUMP + a] = v;
+              }
+            }
+          });
+        });
+      });
+    }
     int tt = 0;
 #pragma unroll
-    for (int ab = 0; ab < CB; ++ab)
+    for (int ab = 0; ab < (kHaG ? 0 : CB); ++ab)
 #pragma unroll
       for (int bb = ab; bb < CB; ++bb, ++tt) {
         const d4 h = hacc[tt];
@@ -941,7 +1067,41 @@ __device__ __forceinline__ void setup_env(
 
   STAMP_END(4);
   STAMP_BEGIN();
-  // (X, H_dv, f_dv and [Hr | g] were stored to the workspace where they were formed)
+  // (X, H_dv, f_dv and [Hr | g] were stored to the workspace where they were formed -- but kHaG:)
+  if constexpr (kHaG) {
+    // The hand-off: the env's block [g | Hr | X | H_dv | f_dv] = workspace doubles 0 .. W_SOL is
+    // four runs of LDS; lane l moves the 16-byte pieces l, l + 64, ... of the block, each trip's
+    // run known at compile time but for the trips that straddle two.  Buffer stores on a
+    // descriptor of exactly this block (a piece past it would be dropped, not written),
+    // write-through (sc1), so the lines are on their way out of this XCD's L2 while the kernel still
+    // runs instead of being written back at the kernel boundary.  Lanes past the last piece
+    // rewrite it with its own value (no branch).
+    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+    constexpr int B1 = D::W_X / 2, B2 = D::W_HD / 2, B3 = D::W_GD / 2, NP = D::W_SOL / 2;
+    constexpr int D0 = D::O_GH_L / 2, D1 = D::O_X_L / 2 - B1, D2 = D::O_HD_L / 2 - B2,
+                  D3 = D::O_FD_L / 2 - B3;
+    static_assert(D::O_GH_L % 2 == 0 && D::O_X_L % 2 == 0, "16-byte pieces");
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        ws + static_cast<size_t>(env) * D::WS, 0, D::W_SOL * 8, 0x00020000);
+    const u4* s4 = reinterpret_cast<const u4*>(sm);
+    constexpr int NT = (NP + kWave - 1) / kWave;
+    u4 v[NT];
+    int at[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int lo = t * kWave, hi = (lo + kWave - 1 < NP - 1) ? lo + kWave - 1 : NP - 1;
+      const int i = (lo + kWave <= NP || lo + lane < NP) ? lo + lane : NP - 1;
+      int d = D3;
+      if (lo < B3) d = (hi < B3 || i < B3) ? D2 : d;
+      if (lo < B2) d = (hi < B2 || i < B2) ? D1 : d;
+      if (lo < B1) d = (hi < B1 || i < B1) ? D0 : d;
+      at[t] = i;
+      v[t] = s4[i + d];
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      __builtin_amdgcn_raw_buffer_store_b128(v[t], rs, 16 * at[t], 0, OSC_SETUP_WT ? 16 : 0);   // (16: sc1)
+  }
   STAMP_END(5);
   STAMP_STORE_SETUP();
 }
