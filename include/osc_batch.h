@@ -43,6 +43,10 @@
  *                                 env the first pass leaves not OK, warm or cold entry -- see
  *                                 OSC_SOLVE_UNREFINED); -k when the wheel rows' active-set
  *                                 fallback solved it in k steps (osc_batch_solve_ex / _warm_ex)
+ * The outputs need only their element's alignment -- tau, x and the duals y 8 bytes, status and
+ * iters 4 -- and so does warm_state (8 bytes; osc_batch_tick_multi asks 16): the kernels access them
+ * element by element, whereas the inputs M, C, J, b, T, mask, wheel_dir and the workspace must be
+ * 16-byte aligned and are refused otherwise (tests/test_gpu_memory_bounds.py holds both).
  *
  * All batch pointers passed to osc_batch_solve are DEVICE pointers (HBM-resident); `stream` is
  * a hipStream_t (NULL = default stream).  The call is asynchronous with respect to the host.

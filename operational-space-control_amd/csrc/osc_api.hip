@@ -356,6 +356,8 @@ int launch(const osc_model* model, int32_t nenv, const double* M, const double* 
   if ((stages & kInteriorPoint) && !tau) return OSC_ERR_INVALID_ARGUMENT;
   const bool wheels = model->kid == K_WALTER_WHEELS;
   if (wheels && (stages & kAssemble) && wdir == nullptr) return OSC_ERR_INVALID_ARGUMENT;
+  // (every entry that takes wheel directions: osc_batch_assemble_ex used to pass them unchecked)
+  if (wdir != nullptr && misaligned16(wdir)) return OSC_ERR_INVALID_ARGUMENT;
   if (y != nullptr && (x == nullptr || (stages & kBoth) != kBoth)) return OSC_ERR_INVALID_ARGUMENT;
   if (y != nullptr && !model->refine) return OSC_ERR_INVALID_ARGUMENT;   // (fused path only)
   // A split call hands the reduced QP over in the caller's workspace; only the fused call may
