@@ -236,6 +236,31 @@ __host__ __device__ constexpr int hr_off(int i, int j) {
   }
 }
 
+// hr_off(i, j) of the compact layout for a column known to lie in the first slot (j < kRow:
+// hr_col_lo) or past it (j >= kRow: hr_col_hi), as a per-lane term in j plus a constant in i --
+// with i a compile-time constant, four per-lane values and immediates serve a lane's two whole
+// columns, and only the packed triangle's entries choose between two of them.
+template <class D>
+__host__ __device__ constexpr unsigned hr_col_lo(int i, unsigned j) {
+  if (i >= kRow) return (i - kRow) * D::NY + j;                     // A, row i
+  const unsigned tj = D::HR_T + j * kRow - j * (j - 1) / 2 - j;     // triangle row j, less j
+  const unsigned ti = D::HR_T + i * kRow - i * (i - 1) / 2 - i;
+  return static_cast<unsigned>(i) <= j ? ti + j : tj + i;
+}
+template <class D>
+__host__ __device__ constexpr unsigned hr_col_hi(int i, unsigned j) {
+  return i >= kRow ? (i - kRow) * D::NY + j : (j - kRow) * D::NY + i;   // A: row i / row j
+}
+template <class D>
+constexpr bool hr_col_offsets_match() {
+  for (int i = 0; i < D::NY; ++i)
+    for (int j = 0; j < D::NY; ++j)
+      if ((j < kRow ? hr_col_lo<D>(i, j) : hr_col_hi<D>(i, j)) !=
+          static_cast<unsigned>(hr_off<D>(i, j)))
+        return false;
+  return true;
+}
+
 // ---- IPM-kernel LDS per env (doubles): workspace prefix [g (| Hr)] + vectors.
 // Large batches (two waves per SIMD): Hr is NOT in LDS -- each lane streams its two Hr columns
 // from the L2-resident workspace into the Newton-matrix registers once per iteration, which

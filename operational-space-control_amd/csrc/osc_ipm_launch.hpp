@@ -110,11 +110,12 @@ __global__ __launch_bounds__(kWave, 1) void osc_ipm_pair_kernel(PairArgs A, Pair
   // (flags bit 0: the cold fix-up pass over the envs left not OK, launched after the solve when
   // refinement is fused -- a second launch: a second inlined body per model spills, launch_pair)
   if (blk < nbA)
-    ipm_block<DA, true, false, RF>(A.P, blk, A.nenv, A.mask, A.ws, A.tau, A.x, A.status,
-                                   A.iters, nullptr, flags & 1, sm);
+    ipm_block<DA, true, false, RF, kCpNone, false, true>(A.P, blk, A.nenv, A.mask, A.ws, A.tau, A.x,
+                                                         A.status, A.iters, nullptr, flags & 1, sm);
   else
-    ipm_block<DB, true, false, RF>(B.P, blk - nbA, B.nenv, B.mask, B.ws, B.tau, B.x,
-                                   B.status, B.iters, nullptr, flags & 1, sm);
+    ipm_block<DB, true, false, RF, kCpNone, false, true>(B.P, blk - nbA, B.nenv, B.mask, B.ws, B.tau,
+                                                         B.x, B.status, B.iters, nullptr, flags & 1,
+                                                         sm);
 }
 
 // One launch of osc_ipm_kernel<D, SMALL, WARM, RF> over the call's wavefronts.  Everything but

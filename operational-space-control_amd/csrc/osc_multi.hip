@@ -62,13 +62,15 @@ void launch_pair_walter_go2(const osc_batch_job& w, const osc_batch_job& g, hipS
 // slower at 4,096 + 4,096 envs (DESIGN.md §8 has both forms' resource numbers and times).
 template <class D, bool W>
 __device__ __forceinline__ void pair_tick_body(const PairArgs& a, int blk, int flags, double* sm) {
-  ipm_block<D, true, W, kRfFused>(a.P, blk, a.nenv, a.mask, a.ws, a.tau, a.x, a.status, a.iters,
-                                  W ? a.warm : nullptr, flags & 1, sm);
+  ipm_block<D, true, W, kRfFused, kCpNone, false, true>(a.P, blk, a.nenv, a.mask, a.ws, a.tau, a.x,
+                                                        a.status, a.iters, W ? a.warm : nullptr,
+                                                        flags & 1, sm);
 #ifndef OSC_PAIR_WARM_TWO_LAUNCHES
   if (flags & 4) {   // (its statuses are the wavefront's own stores: a workgroup-scope fence)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    ipm_block<D, true, W, kRfFused>(a.P, blk, a.nenv, a.mask, a.ws, a.tau, a.x, a.status, a.iters,
-                                    W ? a.warm : nullptr, 1, sm);
+    ipm_block<D, true, W, kRfFused, kCpNone, false, true>(a.P, blk, a.nenv, a.mask, a.ws, a.tau,
+                                                          a.x, a.status, a.iters,
+                                                          W ? a.warm : nullptr, 1, sm);
   }
 #endif
 }

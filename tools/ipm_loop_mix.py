@@ -200,7 +200,10 @@ def analyse(asm: str, kernel: str) -> dict:
     name, blocks = function_blocks(asm, kernel)
     succ = successors(blocks)
     dpp = [sum(m.startswith("v_fmac_f64_dpp") for m in b["ins"]) for b in blocks]
-    ldl = max(range(len(blocks)), key=dpp.__getitem__)
+    # (the first such block that lies on a cycle: a kernel with the start peeled has one more
+    # factorisation, straight-line, ahead of the loop)
+    cyclic = [i for c in loops(range(len(blocks)), succ) for i in c]
+    ldl = max(sorted(cyclic), key=dpp.__getitem__)
     outer = next(c for c in loops(range(len(blocks)), succ) if ldl in c)
     # loops nested in the iteration loop: its cycles once the blocks it is entered at are gone
     # (two of them: the start's iteration enters ahead of the others' stop test)
