@@ -742,6 +742,11 @@ bool env_call_ok(const osc_model* model, const osc_env_params* ep, const osc_sol
 }
 }  // namespace
 
+bool osc::env_tick_ok(const osc_model* model, const osc_env_params* env_params,
+                      const osc_solve_extras* extras) {
+  return env_call_ok(model, env_params, extras);
+}
+
 extern "C" int osc_batch_solve_env(const osc_model* model, int32_t nenv, const double* M,
                                    const double* C, const double* J, const double* b,
                                    const double* T, const double* contact_mask,

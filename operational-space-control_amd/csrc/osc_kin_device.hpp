@@ -49,6 +49,14 @@ struct alignas(16) KinDev {   // alignas: sizeof % 16 == 0 (16-byte LDS staging)
   double site_pos[OSC_KIN_MAX_SITES][3];
 };
 
+// Per-env inertial parameters (include/osc_kin_env_params.h): DEVICE arrays, each nullable (NULL =
+// the model's value).  Read only by the kEnv instantiations below; the others carry none.
+struct KinEnvPtrs {
+  const double* mass_scale;       // [nenv][nbody]
+  const double* com_offset;       // [nenv][nbody][3]
+  const double* armature_scale;   // [nenv][nv]
+};
+
 constexpr int even(int a) { return (a + 1) & ~1; }
 
 struct EnvLayout {   // per-env LDS layout in doubles
@@ -87,7 +95,9 @@ __device__ __forceinline__ void inertia_mul(double m, const double* h, const dou
 }
 
 // Forward pass for body b (its parent's state is final): frame, velocity, bias acceleration,
-// spatial inertia and the body's own RNEA force.  Writes the body's LDS state.
+// spatial inertia and the body's own RNEA force.  Writes the body's LDS state.  (kEnv changes
+// nothing here: a template so that each kernel variant keeps a copy of its own, inlined.)
+template <bool kEnv = false>
 static __device__ void body_forward(const KinDev* K, double* E, const EnvLayout& lay,
                              int b, double s, double c) {
   double R[9], x[3], w[3], vo[3], al[3], ao[3];
@@ -222,8 +232,11 @@ static __device__ void body_forward(const KinDev* K, double* E, const EnvLayout&
 }
 
 // Body b's spatial inertia about the world origin and its own RNEA force, once its frame and
-// motion are in LDS (all bodies in parallel, after the level-by-level pass).
-static __device__ void body_dynamics(const KinDev* K, double* E, const EnvLayout& lay, int b) {
+// motion are in LDS (all bodies in parallel, after the level-by-level pass).  kEnv: the env's mass
+// scale `ms` of this body (m' = ms m, Ib' = ms Ib: density scaling) and COM offset `dc` (body frame).
+template <bool kEnv = false>
+static __device__ void body_dynamics(const KinDev* K, double* E, const EnvLayout& lay, int b,
+                                     double ms = 1.0, const double* dc = nullptr) {
   double* B = E + lay.body + kBodyStride * b;
   double R[9], x[3], w[3], vo[3], al[3], ao[3];
   for (int i = 0; i < 9; ++i) R[i] = B[B_R + i];
@@ -232,9 +245,17 @@ static __device__ void body_dynamics(const KinDev* K, double* E, const EnvLayout
     al[i] = B[B_AL + i]; ao[i] = B[B_AO + i];
   }
   // IO = R Ib R' + m (|c|^2 I - c c'), h = m c
-  const double m = K->mass[b];
+  double m = K->mass[b];
   const double* ip = K->ipos[b];
   const double* ib = K->ib[b];
+  double ipe[3], ibe[6];
+  if constexpr (kEnv) {
+    m *= ms;
+    for (int i = 0; i < 3; ++i) ipe[i] = ip[i] + dc[i];
+    for (int i = 0; i < 6; ++i) ibe[i] = ms * ib[i];
+    ip = ipe;
+    ib = ibe;
+  }
   double c[3];
   for (int i = 0; i < 3; ++i) c[i] = x[i] + R[3 * i] * ip[0] + R[3 * i + 1] * ip[1] + R[3 * i + 2] * ip[2];
   const double Ibf[9] = {ib[0], ib[3], ib[4], ib[3], ib[1], ib[5], ib[4], ib[5], ib[2]};
@@ -280,18 +301,20 @@ static __device__ void body_dynamics(const KinDev* K, double* E, const EnvLayout
 // Stage 1, forward pass level by level (lane = body l; lanes past nbody idle).  Every lane of the
 // wave calls it (wave barriers inside).  Every hinge's sin / cos up front (all lanes at once), so
 // the level loop -- whose body executes once per level -- carries no libm call; the inertia /
-// force work, which needs no parent data, runs once for all bodies after it.
+// force work, which needs no parent data, runs once for all bodies after it.  kEnv: body l's
+// per-env mass scale and COM offset (body_dynamics).
+template <bool kEnv = false>
 __device__ __forceinline__ void kin_forward(const KinDev* K, double* E, const EnvLayout& lay,
-                                            int l) {
+                                            int l, double ms = 1.0, const double* dc = nullptr) {
   const int nb = K->nbody, nd = K->ndepth;
   const int my_depth = (l < nb) ? K->depth[l] : -1;
   double sn = 0.0, cs = 1.0;
   if (l < nb && K->jtype[l] == OSC_KIN_JOINT_HINGE) sincos(E[lay.q + K->qadr[l]], &sn, &cs);
   for (int L = 0; L < nd; ++L) {
-    if (my_depth == L) body_forward(K, E, lay, l, sn, cs);
+    if (my_depth == L) body_forward<kEnv>(K, E, lay, l, sn, cs);
     wave_sync();
   }
-  if (l < nb) body_dynamics(K, E, lay, l);
+  if (l < nb) body_dynamics<kEnv>(K, E, lay, l, ms, dc);
   wave_sync();
 }
 
@@ -432,11 +455,16 @@ constexpr int kKinEnvPerWave = kKinWave / kKinRow;
 // each.  `sK` is the workgroup's LDS copy of the model tables (staged here from Kg), `kin_sm` its
 // 4 * EnvLayout.size doubles of per-env state.  Wrapped by osc_kinematics_kernel (one model) and
 // osc_kinematics_pair_kernel (two models, osc_multi.hip).
+// kEnv (osc_kinematics_env_kernel): per-env inertial parameters `ep`.  Lane = body reads its mass
+// scale and COM offset, lane = column its armature scales, once, before stage 1; a row whose env
+// holds an invalid value (NaN, non-finite, mass scale <= 0, armature scale < 0) writes NaN to every
+// entry of that env's M and C.  J, b and site_xpos do not depend on the parameters.
+template <bool kEnv = false>
 __device__ __forceinline__ void kin_block(
     const KinDev* __restrict__ Kg, KinDev* sK, double* kin_sm, int blk, int nenv,
     const double* __restrict__ qpos, const double* __restrict__ qvel, double* __restrict__ gM,
     double* __restrict__ gC, double* __restrict__ gJ, double* __restrict__ gb,
-    double* __restrict__ gx) {
+    double* __restrict__ gx, KinEnvPtrs ep = {}) {
   constexpr int kWave = kKinWave, kRow = kKinRow, kEnvPerWave = kKinEnvPerWave;
   // The model tables are indexed per lane (body / dof / site differ across lanes), so they are
   // staged into LDS once per workgroup: ~64-cycle LDS reads instead of dependent L2 round trips
@@ -463,9 +491,39 @@ __device__ __forceinline__ void kin_block(
   for (int i = l; i < nv; i += kRow) E[lay.q + nq + i] = qvel[static_cast<size_t>(env) * nv + i];
   wave_sync();
 
+  const int c0 = l, c1 = l + kRow;   // stage 5 / 6: this lane's columns
+  const bool v0 = c0 < nv, v1 = c1 < nv;
+  // (kEnv) this lane's parameters of the row's env -- tail rows read the clamped env's -- and the
+  // row's validity: one ballot, the row's 16 bits of it
+  double ms = 1.0, dc[3] = {0.0, 0.0, 0.0}, as0 = 1.0, as1 = 1.0;
+  bool env_bad = false;
+  if constexpr (kEnv) {
+    bool bad = false;
+    if (l < nb) {
+      const size_t eb = static_cast<size_t>(env) * nb + l;
+      if (ep.mass_scale) {
+        ms = ep.mass_scale[eb];
+        bad = !(ms > 0.0) || !isfinite(ms);
+      }
+      if (ep.com_offset)
+        for (int i = 0; i < 3; ++i) {
+          dc[i] = ep.com_offset[eb * 3 + i];
+          bad = bad || !isfinite(dc[i]);
+        }
+    }
+    if (ep.armature_scale) {
+      const double* as = ep.armature_scale + static_cast<size_t>(env) * nv;
+      if (v0) as0 = as[c0];
+      if (v1) as1 = as[c1];
+      bad = bad || !(as0 >= 0.0) || !isfinite(as0) || !(as1 >= 0.0) || !isfinite(as1);
+    }
+    env_bad = ((__ballot(bad) >> (row * kRow)) & 0xffffull) != 0;
+  }
+  const double kNaN = __builtin_nan("");
+
   KIN_STOP(0);
   // ---- stage 1: forward pass, level by level (lane = body) --------------------------------
-  kin_forward(K, E, lay, l);
+  kin_forward<kEnv>(K, E, lay, l, ms, dc);
 
   KIN_STOP(1);
   // ---- stage 2: backward pass: subtree composite inertia and force ------------------------
@@ -474,7 +532,8 @@ __device__ __forceinline__ void kin_block(
   KIN_STOP(2);
   // ---- stage 3: dofs (lane = dof): motion subspace S, F = Ic S, C = S . f -----------------
   for (int d = l; d < nv; d += kRow) {
-    const double cd = kin_dof(K, E, lay, d);
+    double cd = kin_dof(K, E, lay, d);
+    if constexpr (kEnv) cd = env_bad ? kNaN : cd;
     if (valid) gC[static_cast<size_t>(env) * nv + d] = cd;
   }
 
@@ -502,8 +561,6 @@ __device__ __forceinline__ void kin_block(
   // M_ij = S_lo . (Ic S_hi) for related dofs (lo = min(i, j)); lane j keeps S_j, F_j in
   // registers, row i's S_i, F_i are row-broadcast LDS reads, relations come from per-dof masks
   // (scalar loads).  Every store writes 16 consecutive doubles of one row.
-  const int c0 = l, c1 = l + kRow;
-  const bool v0 = c0 < nv, v1 = c1 < nv;
   double S0[6], F0[6], S1[6], F1[6];
   {
     const double* D0 = E + lay.dof + kDofStride * (v0 ? c0 : 0);
@@ -524,8 +581,13 @@ __device__ __forceinline__ void kin_block(
         Si[t] = Di[t];
         Fi[t] = Di[6 + t];
       }
-      const double m0 = kin_m_entry(rel, arm, i, c0, Si, Fi, S0, F0);
-      const double m1 = kin_m_entry(rel, arm, i, c1, Si, Fi, S1, F1);
+      // (kEnv: the armature acts where i == column, so each column takes this lane's own scale)
+      double m0 = kin_m_entry(rel, kEnv ? arm * as0 : arm, i, c0, Si, Fi, S0, F0);
+      double m1 = kin_m_entry(rel, kEnv ? arm * as1 : arm, i, c1, Si, Fi, S1, F1);
+      if constexpr (kEnv) {
+        m0 = env_bad ? kNaN : m0;
+        m1 = env_bad ? kNaN : m1;
+      }
       if (valid && v0) Mo[i * nv + c0] = m0;
       if (valid && v1) Mo[i * nv + c1] = m1;
     }

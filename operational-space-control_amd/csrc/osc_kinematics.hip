@@ -50,7 +50,9 @@
 #include <dlfcn.h>
 
 #include "osc_batch.h"
+#include "osc_env_params.h"
 #include "osc_kin_device.hpp"
+#include "osc_kin_env_params.h"
 #include "osc_kin_model.hpp"
 #include "osc_kinematics.h"
 #include "osc_qpos.hpp"
@@ -70,6 +72,18 @@ __global__ __launch_bounds__(kWave) void osc_kinematics_kernel(
   extern __shared__ __attribute__((aligned(16))) double kin_sm[];
   __shared__ __attribute__((aligned(16))) KinDev sK;
   kin_block(Kg, &sK, kin_sm, static_cast<int>(blockIdx.x), nenv, qpos, qvel, gM, gC, gJ, gb, gx);
+}
+
+// The same batch with per-env mass scales, COM offsets and armature scales (kin_block<true>;
+// include/osc_kin_env_params.h): a kernel of its own, so that the one above reads no parameters.
+__global__ __launch_bounds__(kWave) void osc_kinematics_env_kernel(
+    const KinDev* __restrict__ Kg, int nenv, const double* __restrict__ qpos,
+    const double* __restrict__ qvel, double* __restrict__ gM, double* __restrict__ gC,
+    double* __restrict__ gJ, double* __restrict__ gb, double* __restrict__ gx, KinEnvPtrs ep) {
+  extern __shared__ __attribute__((aligned(16))) double kin_sm[];
+  __shared__ __attribute__((aligned(16))) KinDev sK;
+  kin_block<true>(Kg, &sK, kin_sm, static_cast<int>(blockIdx.x), nenv, qpos, qvel, gM, gC, gJ, gb,
+                  gx, ep);
 }
 
 constexpr int kPackBlock = 256;
@@ -469,6 +483,50 @@ extern "C" int osc_batch_kinematics(const osc_kin_model* model, int32_t nenv, co
   return hipGetLastError() == hipSuccess ? OSC_OK : OSC_ERR_DEVICE;
 }
 
+// ---- per-env inertial parameters (include/osc_kin_env_params.h) ----
+
+extern "C" int osc_kin_model_nbody(const osc_kin_model* model, int32_t* nbody) {
+  if (!model || !nbody) return OSC_ERR_INVALID_ARGUMENT;
+  *nbody = model->host.nbody;
+  return OSC_OK;
+}
+
+namespace {
+
+bool kin_params_aligned(const osc_kin_env_params* p) {
+  if (p != nullptr)
+    for (const double* a : {p->mass_scale, p->com_offset, p->armature_scale})
+      if ((reinterpret_cast<uintptr_t>(a) & 7u) != 0) return false;
+  return true;
+}
+
+bool kin_params_any(const osc_kin_env_params* p) {
+  return p != nullptr && (p->mass_scale || p->com_offset || p->armature_scale);
+}
+
+}  // namespace
+
+extern "C" int osc_batch_kinematics_env(const osc_kin_model* model, int32_t nenv,
+                                        const double* qpos, const double* qvel,
+                                        const osc_kin_env_params* params, double* M, double* C,
+                                        double* J, double* b, double* site_xpos, void* stream) {
+  if (!kin_params_aligned(params)) return OSC_ERR_INVALID_ARGUMENT;
+  if (!kin_params_any(params))   // the kernel without parameter reads
+    return osc_batch_kinematics(model, nenv, qpos, qvel, M, C, J, b, site_xpos, stream);
+  if (!model || nenv < 0) return OSC_ERR_INVALID_ARGUMENT;
+  if (nenv == 0) return OSC_OK;
+  if (!qpos || !qvel || !M || !C || !J || !b) return OSC_ERR_INVALID_ARGUMENT;
+  const KinDev& k = model->host;
+  const EnvLayout lay(k.nq, k.nv, k.nbody, k.nsite);
+  const size_t lds = sizeof(double) * static_cast<size_t>(lay.size) * kEnvPerWave;
+  const unsigned nblk = static_cast<unsigned>((nenv + kEnvPerWave - 1) / kEnvPerWave);
+  const KinEnvPtrs ep{params->mass_scale, params->com_offset, params->armature_scale};
+  hipLaunchKernelGGL(osc_kinematics_env_kernel, dim3(nblk), dim3(kWave), lds,
+                     static_cast<hipStream_t>(stream), model->dev, nenv, qpos, qvel, M, C, J, b,
+                     site_xpos, ep);
+  return hipGetLastError() == hipSuccess ? OSC_OK : OSC_ERR_DEVICE;
+}
+
 extern "C" int osc_state_to_qpos(int32_t nenv, int32_t nu, const double* body_rotation,
                                  const double* linear_body_velocity,
                                  const double* angular_body_velocity,
@@ -584,4 +642,83 @@ extern "C" int osc_batch_solve_qpos_warm(const osc_model* model, const osc_kin_m
   if (!warm_state) return OSC_ERR_INVALID_ARGUMENT;
   return solve_qpos(model, kin, nenv, qpos, qvel, T, contact_mask, tau, x, status, iters,
                     warm_state, warm_state_bytes, workspace, workspace_bytes, stream);
+}
+
+// ---- the tick with per-env parameters (include/osc_kin_env_params.h) ----
+
+extern "C" int osc_qpos_env_workspace_bytes(const osc_model* model, const osc_kin_model* kin,
+                                            int32_t nenv, size_t* bytes) {
+  // [M | C | J | b | the solve's workspace]: the _env solves hand their reduced QPs over in the
+  // layout of the plain ones (osc_workspace_env_bytes per env), so the sections are the same
+  return osc_qpos_workspace_bytes(model, kin, nenv, bytes);
+}
+
+extern "C" int osc_batch_solve_qpos_env(const osc_model* model, const osc_kin_model* kin,
+                                        int32_t nenv, const double* qpos, const double* qvel,
+                                        const double* T, const double* contact_mask,
+                                        const osc_env_params* env_params,
+                                        const osc_kin_env_params* kin_params,
+                                        const osc_solve_extras* extras, double* tau, double* x,
+                                        int32_t* status, int32_t* iters, double* warm_state,
+                                        size_t warm_state_bytes, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  // ---- every check before the first launch ----
+  int rc = check_pair(model, kin);
+  if (rc != OSC_OK) return rc;
+  if (nenv < 0 || !kin_params_aligned(kin_params)) return OSC_ERR_INVALID_ARGUMENT;
+  if (extras && extras->wheel_dir) return OSC_ERR_INVALID_ARGUMENT;
+  const bool env = env_params != nullptr &&
+                   (env_params->mu || env_params->u_lb || env_params->u_ub || env_params->fz_lb ||
+                    env_params->fz_ub || env_params->w_pos || env_params->w_rot);
+  if (env_params != nullptr && !osc::env_tick_ok(model, env_params, extras))
+    return OSC_ERR_INVALID_ARGUMENT;
+  double* y = extras ? extras->y : nullptr;
+  if (!env && !kin_params_any(kin_params) && y == nullptr)   // today's tick, whichever build
+    return solve_qpos(model, kin, nenv, qpos, qvel, T, contact_mask, tau, x, status, iters,
+                      warm_state, warm_state_bytes, workspace, workspace_bytes, stream);
+  if (nenv == 0) return OSC_OK;
+  if (!qpos || !qvel) return OSC_ERR_INVALID_ARGUMENT;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return OSC_ERR_INVALID_ARGUMENT;
+  const QposWorkspace L(model, kin->host, nenv);
+  if (workspace != nullptr && workspace_bytes < L.total) return OSC_ERR_INVALID_ARGUMENT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(workspace);
+  bool owned = false;
+  if (base == nullptr) {
+    if (hipMallocAsync(reinterpret_cast<void**>(&base), L.total, s) != hipSuccess)
+      return OSC_ERR_DEVICE;
+    owned = true;
+  }
+  // Two kernels in every build (the fused diagnostic tick has no per-env variant): the kinematics
+  // with its parameters, then the solve with its own -- the plain entries when it has none, which
+  // keeps the lockstep compaction of large cold batches.
+  double* M = reinterpret_cast<double*>(base + L.m);
+  double* C = reinterpret_cast<double*>(base + L.c);
+  double* J = reinterpret_cast<double*>(base + L.j);
+  double* b = reinterpret_cast<double*>(base + L.b);
+  rc = osc_batch_kinematics_env(kin, nenv, qpos, qvel, kin_params, M, C, J, b, nullptr, stream);
+  if (rc == OSC_OK) {
+    if (env)
+      rc = warm_state ? osc_batch_solve_warm_env(model, nenv, M, C, J, b, T, contact_mask,
+                                                 env_params, extras, tau, x, status, iters,
+                                                 warm_state, warm_state_bytes, base + L.ws,
+                                                 L.ws_bytes, stream)
+                      : osc_batch_solve_env(model, nenv, M, C, J, b, T, contact_mask, env_params,
+                                            extras, tau, x, status, iters, base + L.ws, L.ws_bytes,
+                                            stream);
+    else if (y != nullptr)
+      rc = warm_state ? osc_batch_solve_warm_ex(model, nenv, M, C, J, b, T, contact_mask, extras,
+                                                tau, x, status, iters, warm_state,
+                                                warm_state_bytes, base + L.ws, L.ws_bytes, stream)
+                      : osc_batch_solve_ex(model, nenv, M, C, J, b, T, contact_mask, extras, tau, x,
+                                           status, iters, base + L.ws, L.ws_bytes, stream);
+    else
+      rc = warm_state ? osc_batch_solve_warm(model, nenv, M, C, J, b, T, contact_mask, tau, x,
+                                             status, iters, warm_state, warm_state_bytes,
+                                             base + L.ws, L.ws_bytes, stream)
+                      : osc_batch_solve(model, nenv, M, C, J, b, T, contact_mask, tau, x, status,
+                                        iters, base + L.ws, L.ws_bytes, stream);
+  }
+  if (owned) (void)hipFreeAsync(base, s);
+  return rc;
 }

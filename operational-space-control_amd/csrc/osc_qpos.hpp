@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "osc_batch.h"
+#include "osc_env_params.h"
 
 namespace osc_kin {
 struct KinDev;
@@ -27,5 +28,10 @@ int solve_qpos_fused(const osc_model* model, const QposArgs& q, int32_t nenv, co
                      const double* contact_mask, double* tau, double* x, int32_t* status,
                      int32_t* iters, double* warm, size_t warm_bytes, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+// What every _env solve entry refuses before anything is enqueued (osc_api.hip env_call_ok), for
+// the joint-state entries of include/osc_kin_env_params.h, which check before their kinematics.
+bool env_tick_ok(const osc_model* model, const osc_env_params* env_params,
+                 const osc_solve_extras* extras);
 
 }  // namespace osc

@@ -29,9 +29,11 @@
 
 #include "osc_batch.h"
 #include "osc_kin_device.hpp"
+#include "osc_kin_env_params.h"
 #include "osc_kin_model.hpp"
 #include "osc_kinematics.h"
 #include "osc_producers.h"
+#include "osc_qpos.hpp"
 #include "osc_rollout.h"
 
 namespace {
@@ -283,12 +285,22 @@ extern "C" int osc_rollout_workspace_bytes(const osc_model* model, const osc_kin
   return OSC_OK;
 }
 
-extern "C" int osc_batch_rollout(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
-                                 const osc_rollout_args* args, void* stream) {
+namespace {
+
+// osc_batch_rollout (both blocks NULL: every tick through osc_batch_solve_qpos(_warm)) and
+// osc_batch_rollout_env (every tick through osc_batch_solve_qpos_env, the blocks held constant)
+int rollout(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
+            const osc_rollout_args* args, const osc_env_params* ep, const osc_kin_env_params* kp,
+            void* stream) {
   // ---- every check before the first launch ----
   osc_model_desc d;
   int rc = check_handles(model, kin, &d);
   if (rc != OSC_OK) return rc;
+  const bool env = ep != nullptr || kp != nullptr;
+  if (ep != nullptr && !osc::env_tick_ok(model, ep, nullptr)) return OSC_ERR_INVALID_ARGUMENT;
+  if (kp != nullptr)
+    for (const double* a : {kp->mass_scale, kp->com_offset, kp->armature_scale})
+      if ((reinterpret_cast<uintptr_t>(a) & 7u) != 0) return OSC_ERR_INVALID_ARGUMENT;
   if (!args || nenv < 0 || args->nticks < 0) return OSC_ERR_INVALID_ARGUMENT;
   if (!(args->dt > 0.0) || !std::isfinite(args->dt)) return OSC_ERR_INVALID_ARGUMENT;
   if (args->flags & ~OSC_ROLLOUT_WARM) return OSC_ERR_INVALID_ARGUMENT;
@@ -359,12 +371,18 @@ extern "C" int osc_batch_rollout(const osc_model* model, const osc_kin_model* ki
       if (rc != OSC_OK) break;
     }
     int32_t* status = args->status_hist ? args->status_hist + n * t : status_ws;
-    rc = warm ? osc_batch_solve_qpos_warm(model, kin, nenv, args->qpos, args->qvel, T,
-                                          args->contact_mask, tau, x, status, nullptr, wstate,
-                                          L.warm_bytes, base + L.qp, L.qp_bytes, stream)
-              : osc_batch_solve_qpos(model, kin, nenv, args->qpos, args->qvel, T,
-                                     args->contact_mask, tau, x, status, nullptr, base + L.qp,
-                                     L.qp_bytes, stream);
+    if (env)
+      rc = osc_batch_solve_qpos_env(model, kin, nenv, args->qpos, args->qvel, T, args->contact_mask,
+                                    ep, kp, nullptr, tau, x, status, nullptr,
+                                    warm ? wstate : nullptr, warm ? L.warm_bytes : 0, base + L.qp,
+                                    L.qp_bytes, stream);
+    else
+      rc = warm ? osc_batch_solve_qpos_warm(model, kin, nenv, args->qpos, args->qvel, T,
+                                            args->contact_mask, tau, x, status, nullptr, wstate,
+                                            L.warm_bytes, base + L.qp, L.qp_bytes, stream)
+                : osc_batch_solve_qpos(model, kin, nenv, args->qpos, args->qvel, T,
+                                       args->contact_mask, tau, x, status, nullptr, base + L.qp,
+                                       L.qp_bytes, stream);
     if (rc != OSC_OK) break;
     StepArgs a = step_args(kin, nenv);
     a.nu = d.nu;
@@ -389,4 +407,24 @@ extern "C" int osc_batch_rollout(const osc_model* model, const osc_kin_model* ki
   }
   if (owned) (void)hipFreeAsync(base, s);
   return rc;
+}
+
+}  // namespace
+
+extern "C" int osc_batch_rollout(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
+                                 const osc_rollout_args* args, void* stream) {
+  return rollout(model, kin, nenv, args, nullptr, nullptr, stream);
+}
+
+// (the tick's workspace is osc_qpos_env_workspace_bytes, which is osc_qpos_workspace_bytes: one
+// layout for both rollouts)
+extern "C" int osc_rollout_env_workspace_bytes(const osc_model* model, const osc_kin_model* kin,
+                                               int32_t nenv, int32_t nticks, size_t* bytes) {
+  return osc_rollout_workspace_bytes(model, kin, nenv, nticks, bytes);
+}
+
+extern "C" int osc_batch_rollout_env(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
+                                     const osc_rollout_args* args, const osc_env_params* env_params,
+                                     const osc_kin_env_params* kin_params, void* stream) {
+  return rollout(model, kin, nenv, args, env_params, kin_params, stream);
 }

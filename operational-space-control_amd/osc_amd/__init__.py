@@ -13,6 +13,9 @@ def __getattr__(name):
     if name in ("OSCBatchSolver", "SolveResult", "EnvParams", "EnvGrads"):
         from . import solver
         return getattr(solver, name)
+    if name in ("KinematicsBatch", "KinEnvParams"):
+        from . import kinematics
+        return getattr(kinematics, name)
     if name in ("solve_differentiable", "solve_differentiable_env"):
         from . import autograd
         return getattr(autograd, name)

@@ -60,6 +60,12 @@ ENV_PARAMS_SYMBOLS = ("osc_batch_solve_env", "osc_batch_solve_warm_env", "osc_ba
 # include/osc_backward_env.h (the backward pass with per-env parameters and their gradients), apart
 # likewise; tests/test_backward_env_ref.py pins this list to that header's declarations.
 BACKWARD_ENV_SYMBOLS = ("osc_batch_solve_backward_env",)
+# include/osc_kin_env_params.h (per-env mass, COM and armature; the joint-state tick and the rollout
+# with per-env parameters), apart likewise; tests/test_kin_env_ref.py pins this list to that
+# header's declarations.
+KIN_ENV_SYMBOLS = ("osc_kin_model_nbody", "osc_batch_kinematics_env",
+                   "osc_qpos_env_workspace_bytes", "osc_batch_solve_qpos_env",
+                   "osc_rollout_env_workspace_bytes", "osc_batch_rollout_env")
 
 OSC_KIN_MAX_BODIES = 16
 OSC_KIN_MAX_DOFS = 32
@@ -106,6 +112,11 @@ class OscEnvParams(ctypes.Structure):
     """osc_env_params (include/osc_env_params.h): device arrays, each nullable."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("mu", "u_lb", "u_ub", "fz_lb", "fz_ub", "w_pos",
                                                 "w_rot")]
+
+
+class OscKinEnvParams(ctypes.Structure):
+    """osc_kin_env_params (include/osc_kin_env_params.h): device arrays, each nullable."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("mass_scale", "com_offset", "armature_scale")]
 
 
 class OscEnvGrads(ctypes.Structure):
@@ -324,6 +335,16 @@ def lib() -> ctypes.CDLL:
     L.osc_rollout_workspace_bytes.restype = ctypes.c_int
     L.osc_batch_rollout.argtypes = [vp, vp, i32, ctypes.POINTER(OscRolloutArgs), vp]
     L.osc_batch_rollout.restype = ctypes.c_int
+    kep, szp = ctypes.POINTER(OscKinEnvParams), ctypes.POINTER(ctypes.c_size_t)
+    L.osc_kin_model_nbody.argtypes = [vp, ip]
+    L.osc_batch_kinematics_env.argtypes = [vp, i32, vp, vp, kep] + [vp] * 5 + [vp]
+    L.osc_qpos_env_workspace_bytes.argtypes = [vp, vp, i32, szp]
+    L.osc_batch_solve_qpos_env.argtypes = [vp, vp, i32] + [vp] * 4 + [ep, kep, xp] + [vp] * 5 + \
+        [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+    L.osc_rollout_env_workspace_bytes.argtypes = [vp, vp, i32, i32, szp]
+    L.osc_batch_rollout_env.argtypes = [vp, vp, i32, ctypes.POINTER(OscRolloutArgs), ep, kep, vp]
+    for name in KIN_ENV_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
     L.osc_batch_solve_backward.argtypes = [vp, i32] + [vp] * 8 + [ctypes.c_size_t, vp]
     L.osc_batch_solve_backward.restype = ctypes.c_int
     L.osc_batch_solve_backward_data.argtypes = [vp, i32] + [vp] * 16 + [ctypes.c_size_t, vp]

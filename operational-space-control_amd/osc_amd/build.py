@@ -68,7 +68,8 @@ def build(verbose: bool = False, force: bool = False, out: str | None = None,
                                                      "osc_kinematics.h", "osc_host_feed.h",
                                                      "osc_rollout.h", "osc_mixed.h",
                                                      "osc_backward.h", "osc_env_params.h",
-                                                     "osc_backward_env.h")] + [__file__]
+                                                     "osc_backward_env.h",
+                                                     "osc_kin_env_params.h")] + [__file__]
     variant = out != OUT
     if not force and os.path.exists(out):
         t_out = os.path.getmtime(out)

@@ -50,6 +50,57 @@ class KinOutputs:
     site_xpos: torch.Tensor | None = None   # (nenv, ns, 3)
 
 
+@dataclasses.dataclass
+class KinEnvParams:
+    """Per-env inertial parameters of the kinematics (osc_kin_env_params,
+    include/osc_kin_env_params.h), each None (= the model's value for every env) or a float64
+    torch tensor / numpy array, env-major:
+      mass_scale (nenv, nbody)       m' = s m and Ib' = s Ib (density scaling)
+      com_offset (nenv, nbody, 3)    ipos' = ipos + d, body frame
+      armature_scale (nenv, nv)      dof_armature' = a dof_armature
+    Shapes and dtypes are checked on the host when a KinematicsBatch takes the block (ValueError
+    before any launch); the values are checked per env on the device, where an invalid env (a NaN
+    or non-finite value, a mass_scale <= 0, an armature_scale < 0) gets NaN M and C, so that its
+    solve returns OSC_SOLVE_NUMERICAL, and leaves the others untouched."""
+    mass_scale: object = None
+    com_offset: object = None
+    armature_scale: object = None
+
+    FIELDS = ("mass_scale", "com_offset", "armature_scale")
+
+    def __post_init__(self):
+        for name in self.FIELDS:
+            a = getattr(self, name)
+            if a is None:
+                continue
+            if not isinstance(a, (np.ndarray, torch.Tensor)):
+                raise TypeError(f"KinEnvParams.{name}: expected torch.Tensor or numpy array")
+            if a.dtype not in (np.float64, torch.float64):
+                raise ValueError(f"KinEnvParams.{name}: expected float64, got {a.dtype}")
+
+    def to_device(self, nenv: int, nbody: int, nv: int, device) -> tuple:
+        """(osc_kin_env_params struct, the device tensors it points to -- keep them alive until
+        the launch is enqueued).  Raises ValueError on a wrong shape, before anything is copied."""
+        want = dict(mass_scale=(nenv, nbody), com_offset=(nenv, nbody, 3),
+                    armature_scale=(nenv, nv))
+        for name in self.FIELDS:
+            a = getattr(self, name)
+            if a is not None and tuple(a.shape) != want[name]:
+                raise ValueError(f"KinEnvParams.{name}: expected shape {want[name]}, got "
+                                 f"{tuple(a.shape)}")
+        c, keep = _lib.OscKinEnvParams(), []
+        for name in self.FIELDS:
+            a = getattr(self, name)
+            if a is None:
+                continue
+            if isinstance(a, np.ndarray):
+                a = torch.from_numpy(np.ascontiguousarray(a))
+            a = a.to(device=device).contiguous()
+            keep.append(a)
+            setattr(c, name, a.data_ptr())
+        return c, keep
+
+
 class KinematicsBatch:
     def __init__(self, robot: str | None = None, tree: dict | None = None,
                  device: torch.device | int | None = None):
@@ -71,6 +122,9 @@ class KinematicsBatch:
         nq, nv, ns = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         _lib.lib().osc_kin_model_dims(h, ctypes.byref(nq), ctypes.byref(nv), ctypes.byref(ns))
         self.nq, self.nv, self.ns = nq.value, nv.value, ns.value
+        nb = ctypes.c_int32()
+        _lib.lib().osc_kin_model_nbody(h, ctypes.byref(nb))
+        self.nbody = nb.value   # after the MJCF reader's split of multi-joint bodies
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -102,9 +156,41 @@ class KinematicsBatch:
                           torch.empty((nenv, s, nv), **o), torch.empty((nenv, s), **o),
                           torch.empty((nenv, self.ns, 3), **o) if want_sites else None)
 
-    def compute_into(self, out: KinOutputs, qpos, qvel, stream=None) -> KinOutputs:
+    def _kin_block(self, kin_params, nenv):
+        """(osc_kin_env_params struct, tensors to keep alive) of a call with kin_params; host-side
+        shape / dtype errors raise here, before any launch."""
+        if not isinstance(kin_params, KinEnvParams):
+            raise TypeError("kin_params: expected a KinEnvParams")
+        return kin_params.to_device(nenv, self.nbody, self.nv, self.device)
+
+    def _blocks(self, solver, env_params, kin_params, nenv):
+        """byref arguments (osc_env_params*, osc_kin_env_params*) of an _env entry -- None = NULL --
+        and what they point to."""
+        keep, e, k = [], None, None
+        if env_params is not None:
+            c, kk = solver._env_block(env_params, nenv)
+            keep += [c] + kk
+            e = ctypes.byref(c)
+        if kin_params is not None:
+            c, kk = self._kin_block(kin_params, nenv)
+            keep += [c] + kk
+            k = ctypes.byref(c)
+        return e, k, keep
+
+    def compute_into(self, out: KinOutputs, qpos, qvel, stream=None,
+                     kin_params=None) -> KinOutputs:
+        """osc_batch_kinematics; with kin_params (a KinEnvParams) osc_batch_kinematics_env."""
         nenv = out.M.shape[0]
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        if kin_params is not None:
+            c, keep = self._kin_block(kin_params, nenv)
+            rc = _lib.lib().osc_batch_kinematics_env(
+                self._h, nenv, ptr(qpos), ptr(qvel), ctypes.byref(c), ptr(out.M), ptr(out.C),
+                ptr(out.J), ptr(out.b), ptr(out.site_xpos),
+                ctypes.c_void_p(self._stream(stream, self.device)))
+            if rc != 0:
+                raise _lib.OSCError("osc_batch_kinematics_env", rc)
+            return out
         rc = _lib.lib().osc_batch_kinematics(self._h, nenv, ptr(qpos), ptr(qvel), ptr(out.M),
                                              ptr(out.C), ptr(out.J), ptr(out.b),
                                              ptr(out.site_xpos),
@@ -113,12 +199,13 @@ class KinematicsBatch:
             raise _lib.OSCError("osc_batch_kinematics", rc)
         return out
 
-    def compute(self, qpos, qvel, want_sites: bool = True) -> KinOutputs:
+    def compute(self, qpos, qvel, want_sites: bool = True, kin_params=None) -> KinOutputs:
         nenv = int(qpos.shape[0])
         qpos = self._dev(qpos, (nenv, self.nq), "qpos")
         qvel = self._dev(qvel, (nenv, self.nv), "qvel")
         with torch.cuda.device(self.device):
-            return self.compute_into(self.alloc(nenv, want_sites), qpos, qvel)
+            return self.compute_into(self.alloc(nenv, want_sites), qpos, qvel,
+                                     kin_params=kin_params)
 
     def state_to_qpos(self, body_rotation, linear_body_velocity, angular_body_velocity,
                       motor_position, motor_velocity, stream=None):
@@ -147,8 +234,38 @@ class KinematicsBatch:
             raise _lib.OSCError("osc_qpos_workspace_bytes", rc)
         return nb.value
 
-    def solve_into(self, solver, out, qpos, qvel, T, mask, workspace, stream=None):
-        """osc_batch_solve_qpos: kinematics + QP assembly + interior point, launch only."""
+    def env_workspace_bytes(self, solver, nenv: int) -> int:
+        nb = ctypes.c_size_t()
+        rc = _lib.lib().osc_qpos_env_workspace_bytes(solver._h, self._h, nenv, ctypes.byref(nb))
+        if rc != 0:
+            raise _lib.OSCError("osc_qpos_env_workspace_bytes", rc)
+        return nb.value
+
+    def _solve_env_into(self, solver, out, warm, qpos, qvel, T, mask, workspace, stream,
+                        env_params, kin_params):
+        """osc_batch_solve_qpos_env (warm None = cold), launch only."""
+        nenv = out.tau.shape[0]
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        e, k, keep = self._blocks(solver, env_params, kin_params, nenv)
+        ex = _lib.OscSolveExtras(None, out.y.data_ptr() if out.y is not None else None)
+        rc = _lib.lib().osc_batch_solve_qpos_env(
+            solver._h, self._h, nenv, ptr(qpos), ptr(qvel), ptr(T), ptr(mask), e, k,
+            ctypes.byref(ex), ptr(out.tau), ptr(out.x), ptr(out.status), ptr(out.iters), ptr(warm),
+            ctypes.c_size_t(0 if warm is None else warm.numel() * 8), ptr(workspace),
+            ctypes.c_size_t(0 if workspace is None else workspace.numel() * 8),
+            ctypes.c_void_p(self._stream(stream, self.device)))
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_solve_qpos_env", rc)
+        return out
+
+    def solve_into(self, solver, out, qpos, qvel, T, mask, workspace, stream=None,
+                   env_params=None, kin_params=None):
+        """osc_batch_solve_qpos: kinematics + QP assembly + interior point, launch only.  With
+        env_params (a solver.EnvParams) or kin_params (a KinEnvParams) osc_batch_solve_qpos_env,
+        its workspace a tensor of env_workspace_bytes."""
+        if env_params is not None or kin_params is not None:
+            return self._solve_env_into(solver, out, None, qpos, qvel, T, mask, workspace, stream,
+                                        env_params, kin_params)
         nenv = out.tau.shape[0]
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         rc = _lib.lib().osc_batch_solve_qpos(
@@ -160,8 +277,15 @@ class KinematicsBatch:
             raise _lib.OSCError("osc_batch_solve_qpos", rc)
         return out
 
-    def solve_warm_into(self, solver, out, warm, qpos, qvel, T, mask, workspace, stream=None):
-        """osc_batch_solve_qpos_warm: the tick from joint states, warm-started from `warm`."""
+    def solve_warm_into(self, solver, out, warm, qpos, qvel, T, mask, workspace, stream=None,
+                        env_params=None, kin_params=None):
+        """osc_batch_solve_qpos_warm: the tick from joint states, warm-started from `warm`.  With
+        env_params or kin_params osc_batch_solve_qpos_env with that warm state."""
+        if env_params is not None or kin_params is not None:
+            if warm is None:
+                raise ValueError("solve_warm_into: warm state required")
+            return self._solve_env_into(solver, out, warm, qpos, qvel, T, mask, workspace, stream,
+                                        env_params, kin_params)
         nenv = out.tau.shape[0]
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         rc = _lib.lib().osc_batch_solve_qpos_warm(
@@ -174,18 +298,24 @@ class KinematicsBatch:
             raise _lib.OSCError("osc_batch_solve_qpos_warm", rc)
         return out
 
-    def solve(self, solver, qpos, qvel, T, mask, want_x: bool = False):
+    def solve(self, solver, qpos, qvel, T, mask, want_x: bool = False, env_params=None,
+              kin_params=None):
         d = solver.dims
         nenv = int(qpos.shape[0])
         qpos = self._dev(qpos, (nenv, self.nq), "qpos")
         qvel = self._dev(qvel, (nenv, self.nv), "qvel")
         T = self._dev(T, (nenv, d["ns"], 6), "T")
         mask = self._dev(mask, (nenv, d["nc"]), "mask")
+        env = env_params is not None or kin_params is not None
+        if env:   # (shape errors: before anything is allocated or launched)
+            self._blocks(solver, env_params, kin_params, nenv)
         out = solver.alloc_outputs(nenv, want_x)
-        ws = torch.empty((max(self.workspace_bytes(solver, nenv) // 8, 2),), dtype=torch.float64,
-                         device=self.device)
+        nbytes = self.env_workspace_bytes(solver, nenv) if env else \
+            self.workspace_bytes(solver, nenv)
+        ws = torch.empty((max(nbytes // 8, 2),), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            return self.solve_into(solver, out, qpos, qvel, T, mask, ws)
+            return self.solve_into(solver, out, qpos, qvel, T, mask, ws, env_params=env_params,
+                                   kin_params=kin_params)
 
     # ---- closed-loop rollout over the controller's own model (include/osc_rollout.h) ----
 
@@ -214,17 +344,18 @@ class KinematicsBatch:
             raise _lib.OSCError("osc_batch_integrate", rc)
         return qpos, qvel
 
-    def rollout_workspace_bytes(self, solver, nenv: int, nticks: int) -> int:
+    def rollout_workspace_bytes(self, solver, nenv: int, nticks: int, env: bool = False) -> int:
+        """osc_rollout_workspace_bytes, or (env) osc_rollout_env_workspace_bytes."""
         nb = ctypes.c_size_t()
-        rc = _lib.lib().osc_rollout_workspace_bytes(solver._h, self._h, nenv, nticks,
-                                                    ctypes.byref(nb))
+        name = "osc_rollout_env_workspace_bytes" if env else "osc_rollout_workspace_bytes"
+        rc = getattr(_lib.lib(), name)(solver._h, self._h, nenv, nticks, ctypes.byref(nb))
         if rc != 0:
-            raise _lib.OSCError("osc_rollout_workspace_bytes", rc)
+            raise _lib.OSCError(name, rc)
         return nb.value
 
     def rollout(self, solver, qpos, qvel, mask, nticks: int, dt: float, T=None, pd=None,
                 warm: bool = True, history: bool = False, stream=None,
-                workspace="alloc") -> "RolloutResult":
+                workspace="alloc", env_params=None, kin_params=None) -> "RolloutResult":
         """osc_batch_rollout: nticks ticks of kinematics -> targets -> solve -> step on the
         device, one enqueue, no host sync.  An idealised rollout over the controller's model, not
         a simulator: no ground, no contact detection, `mask` held constant.
@@ -233,7 +364,9 @@ class KinematicsBatch:
         (4,) shared or (nenv, 3) / (nenv, 4) per env; gains (kp_lin, kd_lin, kp_ang, kd_ang)).
         Inputs (torch tensors or numpy arrays) are copied: the caller's arrays are not modified.
         workspace: "alloc" = a tensor of rollout_workspace_bytes, None = the library's
-        stream-ordered scratch, or a float64 device tensor."""
+        stream-ordered scratch, or a float64 device tensor.
+        env_params (a solver.EnvParams) / kin_params (a KinEnvParams): osc_batch_rollout_env, both
+        blocks held constant over the rollout; an env with invalid parameters stays frozen."""
         if (T is None) == (pd is None):
             raise ValueError("exactly one of T and pd must be given")
         d = solver.dims
@@ -245,6 +378,10 @@ class KinematicsBatch:
         a = _lib.OscRolloutArgs()
         a.nticks, a.dt, a.flags = nticks, float(dt), _lib.ROLLOUT_WARM if warm else 0
         keep = [qpos, qvel, mask]
+        env = env_params is not None or kin_params is not None
+        ep, kp, blocks = self._blocks(solver, env_params, kin_params, nenv) if env else \
+            (None, None, [])
+        keep += blocks
         if T is not None:
             T = self._dev(T, (nenv, d["ns"], 6), "T")
             a.target_mode, a.T = _lib.ROLLOUT_TARGETS_HELD, T.data_ptr()
@@ -272,17 +409,21 @@ class KinematicsBatch:
             a.qpos_hist, a.qvel_hist = res.qpos_hist.data_ptr(), res.qvel_hist.data_ptr()
             a.tau_hist, a.status_hist = res.tau_hist.data_ptr(), res.status_hist.data_ptr()
         if isinstance(workspace, str):
-            workspace = torch.empty((max(self.rollout_workspace_bytes(solver, nenv, nslab) // 8,
-                                         2),), **o)
+            workspace = torch.empty((max(self.rollout_workspace_bytes(solver, nenv, nslab,
+                                                                      env=env) // 8, 2),), **o)
         if workspace is not None:
             a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
         a.contact_mask, a.qpos, a.qvel = mask.data_ptr(), qpos.data_ptr(), qvel.data_ptr()
         a.tau, a.bad_ticks = res.tau.data_ptr(), res.bad_ticks.data_ptr()
+        s = ctypes.c_void_p(self._stream(stream, self.device))
         with torch.cuda.device(self.device):
-            rc = _lib.lib().osc_batch_rollout(solver._h, self._h, nenv, ctypes.byref(a),
-                                              ctypes.c_void_p(self._stream(stream, self.device)))
+            if env:
+                rc = _lib.lib().osc_batch_rollout_env(solver._h, self._h, nenv, ctypes.byref(a),
+                                                      ep, kp, s)
+            else:
+                rc = _lib.lib().osc_batch_rollout(solver._h, self._h, nenv, ctypes.byref(a), s)
         if rc != 0:
-            raise _lib.OSCError("osc_batch_rollout", rc)
+            raise _lib.OSCError("osc_batch_rollout_env" if env else "osc_batch_rollout", rc)
         res._keep = keep + [workspace]   # inputs and scratch stay alive until the stream is done
         return res
 
