@@ -91,8 +91,10 @@ int osc_batch_solve_backward(const osc_model* model, int32_t nenv, const double*
  * osc_batch_solve_backward (a model with wheel rows is refused; all checks before any launch;
  * nenv == 0 is OSC_OK).  Gradients with respect to the bounds, mu and the site weights, and the
  * backward pass of a batch solved with per-env parameters (osc_env_params.h):
- * osc_batch_solve_backward_env, osc_backward_env.h.  Backward passes of the joint-state, multi,
- * host-fed and wheel-row entries remain out of scope. */
+ * osc_batch_solve_backward_env, osc_backward_env.h.  From joint states, the kinematics' own backward
+ * pass (osc_batch_kinematics_backward, osc_kin_backward.h) takes grad_M, grad_C, grad_J and grad_b
+ * on to qpos, qvel and the per-env inertial parameters.  Backward passes of the multi, host-fed
+ * and wheel-row entries remain out of scope. */
 int osc_batch_solve_backward_data(const osc_model* model, int32_t nenv, const double* M,
                                   const double* J, const double* b, const double* T,
                                   const double* contact_mask, const double* x, const double* y,

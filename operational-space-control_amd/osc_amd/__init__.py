@@ -13,10 +13,11 @@ def __getattr__(name):
     if name in ("OSCBatchSolver", "SolveResult", "EnvParams", "EnvGrads"):
         from . import solver
         return getattr(solver, name)
-    if name in ("KinematicsBatch", "KinEnvParams"):
+    if name in ("KinematicsBatch", "KinEnvParams", "KinEnvGrads"):
         from . import kinematics
         return getattr(kinematics, name)
-    if name in ("solve_differentiable", "solve_differentiable_env"):
+    if name in ("solve_differentiable", "solve_differentiable_env", "kinematics_differentiable",
+                "solve_differentiable_qpos"):
         from . import autograd
         return getattr(autograd, name)
     raise AttributeError(name)

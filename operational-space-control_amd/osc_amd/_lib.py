@@ -66,6 +66,9 @@ BACKWARD_ENV_SYMBOLS = ("osc_batch_solve_backward_env",)
 KIN_ENV_SYMBOLS = ("osc_kin_model_nbody", "osc_batch_kinematics_env",
                    "osc_qpos_env_workspace_bytes", "osc_batch_solve_qpos_env",
                    "osc_rollout_env_workspace_bytes", "osc_batch_rollout_env")
+# include/osc_kin_backward.h (the kinematics' backward pass), apart likewise;
+# tests/test_kin_backward_ref.py pins this list to that header's declarations.
+KIN_BACKWARD_SYMBOLS = ("osc_batch_kinematics_backward",)
 
 OSC_KIN_MAX_BODIES = 16
 OSC_KIN_MAX_DOFS = 32
@@ -116,6 +119,11 @@ class OscEnvParams(ctypes.Structure):
 
 class OscKinEnvParams(ctypes.Structure):
     """osc_kin_env_params (include/osc_kin_env_params.h): device arrays, each nullable."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("mass_scale", "com_offset", "armature_scale")]
+
+
+class OscKinEnvGrads(ctypes.Structure):
+    """osc_kin_env_grads (include/osc_kin_backward.h): device output arrays, each nullable."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("mass_scale", "com_offset", "armature_scale")]
 
 
@@ -345,6 +353,9 @@ def lib() -> ctypes.CDLL:
     L.osc_batch_rollout_env.argtypes = [vp, vp, i32, ctypes.POINTER(OscRolloutArgs), ep, kep, vp]
     for name in KIN_ENV_SYMBOLS:
         getattr(L, name).restype = ctypes.c_int
+    L.osc_batch_kinematics_backward.argtypes = [vp, i32, vp, vp, kep] + [vp] * 7 + \
+        [ctypes.POINTER(OscKinEnvGrads), vp]
+    L.osc_batch_kinematics_backward.restype = ctypes.c_int
     L.osc_batch_solve_backward.argtypes = [vp, i32] + [vp] * 8 + [ctypes.c_size_t, vp]
     L.osc_batch_solve_backward.restype = ctypes.c_int
     L.osc_batch_solve_backward_data.argtypes = [vp, i32] + [vp] * 16 + [ctypes.c_size_t, vp]

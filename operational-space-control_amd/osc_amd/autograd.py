@@ -20,11 +20,20 @@ With per-env parameters (solver.EnvParams; include/osc_backward_env.h, DESIGN.md
     p = EnvParams(mu=mu, fz_ub=cap, w_pos=w)     # tensors with requires_grad get a gradient
     tau, x, status = solve_differentiable_env(solver, M, C, J, b, T, mask, p)
     loss(tau, x).backward()        # mu.grad, cap.grad, w.grad, T.grad, b.grad
+
+Through the kinematics front end (include/osc_kin_backward.h), for callers who
+hold qpos / qvel on the device:
+
+    M, C, J, b = kinematics_differentiable(kin, qpos, qvel)            # kin: a KinematicsBatch
+    tau, x, status = solve_differentiable_qpos(solver, kin, qpos, qvel, T, mask,
+                                               kin_params=KinEnvParams(mass_scale=s))
+    loss(tau, x).backward()        # qpos.grad, qvel.grad, s.grad, T.grad: two backward launches
 """
 from __future__ import annotations
 
 import torch
 
+from .kinematics import KinEnvGrads, KinEnvParams, KinematicsBatch
 from .solver import EnvGrads, EnvParams, OSCBatchSolver
 
 
@@ -192,3 +201,82 @@ def solve_differentiable_env(solver: OSCBatchSolver, M, C, J, b, T, mask, env_pa
     x, status = _OSCSolveEnv.apply(solver, env_params, M, C, J, b, T, mask, *fields)
     d = solver.dims
     return x[:, d["nv"]:d["nv"] + d["nu"]], x, status
+
+
+class _Kinematics(torch.autograd.Function):
+    """osc_batch_kinematics(_env); the three KinEnvParams fields follow qpos and qvel as explicit
+    inputs (a tensor, or None for a field that is absent, a numpy array or needs no gradient)."""
+
+    @staticmethod
+    def forward(ctx, kin, kin_params, want_sites, qpos, qvel, *fields):
+        nenv = int(qpos.shape[0])
+        out = kin.alloc(nenv, want_sites)
+        with torch.cuda.device(kin.device):
+            kin.compute_into(out, qpos, qvel, kin_params=kin_params)
+        ctx.kin, ctx.kin_params, ctx.want_sites = kin, kin_params, want_sites
+        ctx.save_for_backward(qpos, qvel)
+        if want_sites:
+            return out.M, out.C, out.J, out.b, out.site_xpos
+        return out.M, out.C, out.J, out.b
+
+    @staticmethod
+    def backward(ctx, *grads):
+        kin = ctx.kin
+        qpos, qvel = ctx.saved_tensors
+        nenv = int(qpos.shape[0])
+        need_q, need_v = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        need_p = [k for k, n in zip(KinEnvParams.FIELDS, ctx.needs_input_grad[5:8]) if n]
+        if all(g is None for g in grads) or not (need_q or need_v or need_p):
+            return (None,) * 8
+        g = [None if t is None else t.to(dtype=torch.float64).contiguous() for t in grads]
+        g += [None] * (5 - len(g))
+        opts = dict(dtype=torch.float64, device=kin.device)
+        gq = torch.empty((nenv, kin.nq), **opts) if need_q else None
+        gv = torch.empty((nenv, kin.nv), **opts) if need_v else None
+        kg = KinEnvGrads.empty(nenv, kin.nbody, kin.nv, kin.device, need_p) if need_p else None
+        with torch.cuda.device(kin.device):
+            kin.backward_into(qpos, qvel, grad_M=g[0], grad_C=g[1], grad_J=g[2], grad_b=g[3],
+                              grad_site_xpos=g[4], grad_qpos=gq, grad_qvel=gv,
+                              kin_params=ctx.kin_params, kin_grads=kg)
+        return (None, None, None, gq, gv,
+                *(getattr(kg, k) if kg is not None else None for k in KinEnvParams.FIELDS))
+
+
+def kinematics_differentiable(kin: KinematicsBatch, qpos, qvel, kin_params=None,
+                              want_sites: bool = False):
+    """(M, C, J, b[, site_xpos]) of the batch (KinematicsBatch.compute_into), differentiable with
+    respect to qpos (the raw nq coordinates: a quaternion's gradient is orthogonal to it), qvel
+    and the fields of kin_params (a KinEnvParams) that are torch tensors with requires_grad --
+    float64, on kin's device, ValueError otherwise; a numpy field, or a tensor without
+    requires_grad, gets none (its .grad stays None).  The backward is one launch
+    (osc_batch_kinematics_backward) that fills only what autograd asks for; an env with invalid
+    parameters contributes zero gradients.  M's cotangent treats all nv^2 entries as independent."""
+    if kin_params is not None and not isinstance(kin_params, KinEnvParams):
+        raise TypeError("kinematics_differentiable: kin_params must be a KinEnvParams")
+    nenv = int(qpos.shape[0])
+    qpos = kin._dev(qpos, (nenv, kin.nq), "qpos")
+    qvel = kin._dev(qvel, (nenv, kin.nv), "qvel")
+    fields = []
+    for name in KinEnvParams.FIELDS:
+        a = getattr(kin_params, name) if kin_params is not None else None
+        if isinstance(a, torch.Tensor) and a.requires_grad:
+            if a.device != kin.device:
+                raise ValueError(f"kinematics_differentiable: KinEnvParams.{name} requires a "
+                                 f"gradient and must be on {kin.device}")
+            fields.append(a)
+        else:
+            fields.append(None)
+    return _Kinematics.apply(kin, kin_params, bool(want_sites), qpos, qvel, *fields)
+
+
+def solve_differentiable_qpos(solver: OSCBatchSolver, kin: KinematicsBatch, qpos, qvel, T, mask,
+                              env_params=None, kin_params=None):
+    """(tau, x, status) of the joint-state tick (KinematicsBatch.solve: its forward values,
+    bitwise), differentiable with respect to qpos, qvel, T and the tensor fields of kin_params
+    and env_params that require a gradient: kinematics_differentiable composed with
+    solve_differentiable(data_grads=True), or with solve_differentiable_env(data_grads=True) when
+    env_params (a solver.EnvParams) is given.  Two backward launches."""
+    M, C, J, b = kinematics_differentiable(kin, qpos, qvel, kin_params=kin_params)
+    if env_params is not None:
+        return solve_differentiable_env(solver, M, C, J, b, T, mask, env_params, data_grads=True)
+    return solve_differentiable(solver, M, C, J, b, T, mask, data_grads=True)

@@ -101,6 +101,23 @@ class KinEnvParams:
         return c, keep
 
 
+@dataclasses.dataclass
+class KinEnvGrads:
+    """Gradient outputs of KinematicsBatch.backward_into with respect to the per-env parameters
+    (osc_kin_env_grads, include/osc_kin_backward.h): float64 device tensors in KinEnvParams'
+    shapes, each None (= not computed)."""
+    mass_scale: torch.Tensor | None = None
+    com_offset: torch.Tensor | None = None
+    armature_scale: torch.Tensor | None = None
+
+    @classmethod
+    def empty(cls, nenv: int, nbody: int, nv: int, device, fields) -> "KinEnvGrads":
+        shape = dict(mass_scale=(nenv, nbody), com_offset=(nenv, nbody, 3),
+                     armature_scale=(nenv, nv))
+        return cls(**{k: torch.empty(shape[k], dtype=torch.float64, device=device)
+                      for k in fields})
+
+
 class KinematicsBatch:
     def __init__(self, robot: str | None = None, tree: dict | None = None,
                  device: torch.device | int | None = None):
@@ -198,6 +215,57 @@ class KinematicsBatch:
         if rc != 0:
             raise _lib.OSCError("osc_batch_kinematics", rc)
         return out
+
+    def backward_into(self, qpos, qvel, grad_M=None, grad_C=None, grad_J=None, grad_b=None,
+                      grad_site_xpos=None, grad_qpos=None, grad_qvel=None, kin_params=None,
+                      kin_grads=None, stream=None):
+        """osc_batch_kinematics_backward (include/osc_kin_backward.h), launch only: the
+        vector-Jacobian product of compute_into.  grad_M .. grad_site_xpos are the cotangents
+        (None = zero), grad_qpos (nenv, nq) / grad_qvel (nenv, nv) the outputs (None = not
+        computed), kin_params the forward call's KinEnvParams, kin_grads a KinEnvGrads whose
+        non-None fields are filled.  All float64 contiguous tensors on this device."""
+        nenv = int(qpos.shape[0])
+        nv, s = self.nv, 6 * self.ns
+        want = dict(qpos=(nenv, self.nq), qvel=(nenv, nv), grad_M=(nenv, nv, nv),
+                    grad_C=(nenv, nv), grad_J=(nenv, s, nv), grad_b=(nenv, s),
+                    grad_site_xpos=(nenv, self.ns, 3), grad_qpos=(nenv, self.nq),
+                    grad_qvel=(nenv, nv), mass_scale=(nenv, self.nbody),
+                    com_offset=(nenv, self.nbody, 3), armature_scale=(nenv, nv))
+        got = dict(qpos=qpos, qvel=qvel, grad_M=grad_M, grad_C=grad_C, grad_J=grad_J,
+                   grad_b=grad_b, grad_site_xpos=grad_site_xpos, grad_qpos=grad_qpos,
+                   grad_qvel=grad_qvel)
+        if kin_grads is not None:
+            if not isinstance(kin_grads, KinEnvGrads):
+                raise TypeError("kin_grads: expected a KinEnvGrads")
+            got.update({n: getattr(kin_grads, n) for n in KinEnvParams.FIELDS})
+        for name, t in got.items():
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or \
+                    t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{name}: expected a contiguous float64 tensor on {self.device}")
+            if tuple(t.shape) != want[name]:
+                raise ValueError(f"{name}: expected shape {want[name]}, got {tuple(t.shape)}")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        kp, keep = None, []
+        if kin_params is not None:
+            c, keep = self._kin_block(kin_params, nenv)
+            keep.append(c)
+            kp = ctypes.byref(c)
+        kg = None
+        if kin_grads is not None:
+            cg = _lib.OscKinEnvGrads()
+            for n in KinEnvParams.FIELDS:
+                t = getattr(kin_grads, n)
+                setattr(cg, n, t.data_ptr() if t is not None else None)
+            kg = ctypes.byref(cg)
+        rc = _lib.lib().osc_batch_kinematics_backward(
+            self._h, nenv, ptr(qpos), ptr(qvel), kp, ptr(grad_M), ptr(grad_C), ptr(grad_J),
+            ptr(grad_b), ptr(grad_site_xpos), ptr(grad_qpos), ptr(grad_qvel), kg,
+            ctypes.c_void_p(self._stream(stream, self.device)))
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_kinematics_backward", rc)
+        return grad_qpos, grad_qvel
 
     def compute(self, qpos, qvel, want_sites: bool = True, kin_params=None) -> KinOutputs:
         nenv = int(qpos.shape[0])
