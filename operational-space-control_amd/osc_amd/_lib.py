@@ -69,6 +69,10 @@ KIN_ENV_SYMBOLS = ("osc_kin_model_nbody", "osc_batch_kinematics_env",
 # include/osc_kin_backward.h (the kinematics' backward pass), apart likewise;
 # tests/test_kin_backward_ref.py pins this list to that header's declarations.
 KIN_BACKWARD_SYMBOLS = ("osc_batch_kinematics_backward",)
+# include/osc_rollout_backward.h (the rollout's backward pass), apart likewise;
+# tests/test_rollout_backward_ref.py pins this list to that header's declarations.
+ROLLOUT_BACKWARD_SYMBOLS = ("osc_batch_integrate_backward", "osc_pd_base_targets_backward",
+                            "osc_rollout_backward_workspace_bytes", "osc_batch_rollout_backward")
 
 OSC_KIN_MAX_BODIES = 16
 OSC_KIN_MAX_DOFS = 32
@@ -210,6 +214,20 @@ class OscRolloutArgs(ctypes.Structure):
         [(n, ctypes.c_void_p) for n in ("contact_mask", "qpos", "qvel", "tau", "qpos_hist",
                                          "qvel_hist", "tau_hist", "status_hist", "bad_ticks",
                                          "workspace")] + [("workspace_bytes", ctypes.c_size_t)]
+
+
+class OscRolloutBackwardArgs(ctypes.Structure):
+    """osc_rollout_backward_args (include/osc_rollout_backward.h)."""
+    _fields_ = [("nticks", ctypes.c_int32), ("dt", ctypes.c_double),
+                ("target_mode", ctypes.c_int32), ("T", ctypes.c_void_p),
+                ("pos_ref", ctypes.c_void_p), ("pos_ref_per_env", ctypes.c_int32),
+                ("quat_ref", ctypes.c_void_p), ("quat_ref_per_env", ctypes.c_int32),
+                ("gains", ctypes.c_double * 4)] + \
+        [(n, ctypes.c_void_p) for n in ("contact_mask", "qpos_hist", "qvel_hist", "status_hist",
+                                         "grad_qpos_hist", "grad_qvel_hist", "grad_tau_hist",
+                                         "grad_qpos0", "grad_qvel0", "grad_T")] + \
+        [("env_grads", ctypes.POINTER(OscEnvGrads)), ("kin_grads", ctypes.POINTER(OscKinEnvGrads)),
+         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
 FEED_QP, FEED_JOINT_STATES, FEED_WARM = 0, 1, 1
@@ -356,6 +374,14 @@ def lib() -> ctypes.CDLL:
     L.osc_batch_kinematics_backward.argtypes = [vp, i32, vp, vp, kep] + [vp] * 7 + \
         [ctypes.POINTER(OscKinEnvGrads), vp]
     L.osc_batch_kinematics_backward.restype = ctypes.c_int
+    L.osc_batch_integrate_backward.argtypes = [vp, i32, ctypes.c_double, vp, vp, vp, vp,
+                                               ctypes.c_int64] + [vp] * 5 + [ctypes.c_int64, vp]
+    L.osc_pd_base_targets_backward.argtypes = [i32, i32, vp, vp, i32] + [vp] * 7
+    L.osc_rollout_backward_workspace_bytes.argtypes = [vp, vp, i32, szp]
+    L.osc_batch_rollout_backward.argtypes = [vp, vp, i32, ctypes.POINTER(OscRolloutBackwardArgs),
+                                             ep, kep, vp]
+    for name in ROLLOUT_BACKWARD_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
     L.osc_batch_solve_backward.argtypes = [vp, i32] + [vp] * 8 + [ctypes.c_size_t, vp]
     L.osc_batch_solve_backward.restype = ctypes.c_int
     L.osc_batch_solve_backward_data.argtypes = [vp, i32] + [vp] * 16 + [ctypes.c_size_t, vp]

@@ -280,3 +280,83 @@ def solve_differentiable_qpos(solver: OSCBatchSolver, kin: KinematicsBatch, qpos
     if env_params is not None:
         return solve_differentiable_env(solver, M, C, J, b, T, mask, env_params, data_grads=True)
     return solve_differentiable(solver, M, C, J, b, T, mask, data_grads=True)
+
+
+class _Rollout(torch.autograd.Function):
+    """KinematicsBatch.rollout with histories; qpos, qvel, the held T (or None) and the seven
+    EnvParams and three KinEnvParams fields follow as explicit inputs (a tensor, or None for a
+    field that is absent, a numpy array or needs no gradient)."""
+
+    NFIXED = 9   # solver .. kin_params
+
+    @staticmethod
+    def forward(ctx, solver, kin, mask, nticks, dt, pd, warm, env_params, kin_params, qpos, qvel,
+                T, *fields):
+        res = kin.rollout(solver, qpos, qvel, mask, nticks, dt, T=T, pd=pd, warm=warm,
+                          history=True, env_params=env_params, kin_params=kin_params)
+        ctx.call = (solver, kin, mask, dt, pd, env_params, kin_params, T)
+        ctx.res = res
+        ctx.mark_non_differentiable(res.status_hist)
+        return res.qpos_hist, res.qvel_hist, res.tau_hist, res.status_hist
+
+    @staticmethod
+    def backward(ctx, gq, gv, gt, _grad_status):
+        solver, kin, mask, dt, pd, env_params, kin_params, T = ctx.call
+        names = ("qpos0", "qvel0", "T") + tuple("env." + k for k in EnvParams.FIELDS) + \
+            tuple("kin." + k for k in KinEnvParams.FIELDS)
+        need = ctx.needs_input_grad[_Rollout.NFIXED:]
+        want = tuple(n for n, w in zip(names, need) if w)
+        none = (None,) * (_Rollout.NFIXED + len(names))
+        if not want or all(g is None for g in (gq, gv, gt)):
+            return none
+        cot = [None if g is None else g.to(dtype=torch.float64).contiguous() for g in (gq, gv, gt)]
+        g = kin.rollout_backward(solver, ctx.res, mask, dt, T=T, pd=pd, grad_qpos_hist=cot[0],
+                                 grad_qvel_hist=cot[1], grad_tau_hist=cot[2],
+                                 env_params=env_params, kin_params=kin_params, want=want)
+        return none[:_Rollout.NFIXED] + tuple(g.get(n) for n in names)
+
+
+def rollout_differentiable(solver: OSCBatchSolver, kin: KinematicsBatch, qpos, qvel, mask,
+                           nticks: int, dt: float, T=None, pd=None, warm: bool = True,
+                           env_params=None, kin_params=None):
+    """(qpos_hist, qvel_hist, tau_hist, status_hist) of the closed-loop rollout
+    (KinematicsBatch.rollout(..., history=True): its forward values, bitwise), differentiable with
+    respect to qpos, qvel, a held T and the tensor fields of env_params (a solver.EnvParams) and
+    kin_params (a KinEnvParams) that require a gradient -- float64, on kin's device, ValueError
+    otherwise; a numpy field, or a tensor without requires_grad, gets none.  Exactly one of T
+    (held targets) and pd = (pos_ref, quat_ref, gains); the PD references and gains, dt and the
+    mask get no gradient.  The backward is one call (osc_batch_rollout_backward,
+    include/osc_rollout_backward.h) that recomputes the ticks from the histories and fills only
+    what autograd asks for; a loss may touch any slab of the three histories.  The gradient with
+    respect to qpos is with respect to the raw nq coordinates."""
+    if env_params is not None and not isinstance(env_params, EnvParams):
+        raise TypeError("rollout_differentiable: env_params must be an EnvParams")
+    if kin_params is not None and not isinstance(kin_params, KinEnvParams):
+        raise TypeError("rollout_differentiable: kin_params must be a KinEnvParams")
+    if (T is None) == (pd is None):
+        raise ValueError("rollout_differentiable: exactly one of T and pd must be given")
+    if pd is not None:
+        for r in pd[:2]:
+            if isinstance(r, torch.Tensor) and r.requires_grad:
+                raise ValueError("rollout_differentiable: no gradient with respect to the PD "
+                                 "references")
+    d = solver.dims
+    nenv = int(qpos.shape[0])
+    qpos = kin._dev(qpos, (nenv, kin.nq), "qpos")
+    qvel = kin._dev(qvel, (nenv, kin.nv), "qvel")
+    if T is not None:
+        T = kin._dev(T, (nenv, d["ns"], 6), "T")
+    fields = []
+    for block, cls, label in ((env_params, EnvParams, "EnvParams"),
+                              (kin_params, KinEnvParams, "KinEnvParams")):
+        for name in cls.FIELDS:
+            a = getattr(block, name) if block is not None else None
+            if isinstance(a, torch.Tensor) and a.requires_grad:
+                if a.device != kin.device:
+                    raise ValueError(f"rollout_differentiable: {label}.{name} requires a gradient "
+                                     f"and must be on {kin.device}")
+                fields.append(a)
+            else:
+                fields.append(None)
+    return _Rollout.apply(solver, kin, mask, int(nticks), float(dt), pd, bool(warm), env_params,
+                          kin_params, qpos, qvel, T, *fields)

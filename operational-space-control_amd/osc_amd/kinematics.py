@@ -495,6 +495,167 @@ class KinematicsBatch:
         res._keep = keep + [workspace]   # inputs and scratch stay alive until the stream is done
         return res
 
+    # ---- the rollout's backward pass (include/osc_rollout_backward.h) ----
+
+    def _grad_tensor(self, t, shape, name, dtype=torch.float64):
+        """A launch-only argument: None, or a contiguous tensor of `dtype` and `shape` here."""
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or \
+                not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous {dtype} tensor on {self.device}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    def integrate_backward_into(self, qpos, qvel_new, qacc, dt, status=None, grad_qpos_new=None,
+                                grad_qvel_new=None, grad_qpos=None, grad_qvel=None, grad_qacc=None,
+                                stream=None):
+        """osc_batch_integrate_backward, launch only: the vector-Jacobian product of integrate_into.
+        qpos is the step's input, qvel_new its output velocity, qacc (nenv, nv) its accelerations
+        (a strided view with contiguous rows is fine; read for the freeze rule only), status the
+        status it was given.  grad_qpos_new / grad_qvel_new are the cotangents (None = zero);
+        grad_qpos, grad_qvel and grad_qacc (which may be a strided view like qacc) the outputs
+        (None = not computed).  A frozen env passes its cotangents through and gets grad_qacc 0."""
+        nenv = int(qpos.shape[0])
+        for name, t in (("qacc", qacc), ("grad_qacc", grad_qacc)):
+            if t is not None and (t.dim() != 2 or tuple(t.shape) != (nenv, self.nv) or
+                                  (self.nv > 1 and t.stride(1) != 1) or
+                                  t.dtype != torch.float64 or t.device != self.device):
+                raise ValueError(f"{name}: expected float64 (nenv, {self.nv}) with contiguous rows "
+                                 f"on {self.device}")
+        sq, sv = (nenv, self.nq), (nenv, self.nv)
+        qpos = self._grad_tensor(qpos, sq, "qpos")
+        qvel_new = self._grad_tensor(qvel_new, sv, "qvel_new")
+        status = self._grad_tensor(status, (nenv,), "status", torch.int32)
+        gqn = self._grad_tensor(grad_qpos_new, sq, "grad_qpos_new")
+        gvn = self._grad_tensor(grad_qvel_new, sv, "grad_qvel_new")
+        gq = self._grad_tensor(grad_qpos, sq, "grad_qpos")
+        gv = self._grad_tensor(grad_qvel, sv, "grad_qvel")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        stride = lambda t: t.stride(0) if t is not None and nenv > 1 else self.nv
+        rc = _lib.lib().osc_batch_integrate_backward(
+            self._h, nenv, float(dt), ptr(qpos), ptr(qvel_new), ptr(status), ptr(qacc),
+            stride(qacc), ptr(gqn), ptr(gvn), ptr(gq), ptr(gv), ptr(grad_qacc), stride(grad_qacc),
+            ctypes.c_void_p(self._stream(stream, self.device)))
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_integrate_backward", rc)
+        return grad_qpos, grad_qvel, grad_qacc
+
+    def rollout_backward_workspace_bytes(self, solver, nenv: int) -> int:
+        nb = ctypes.c_size_t()
+        rc = _lib.lib().osc_rollout_backward_workspace_bytes(solver._h, self._h, nenv,
+                                                             ctypes.byref(nb))
+        if rc != 0:
+            raise _lib.OSCError("osc_rollout_backward_workspace_bytes", rc)
+        return nb.value
+
+    ROLLOUT_GRADS = ("qpos0", "qvel0", "T") + \
+        tuple("env." + k for k in ("mu", "u_lb", "u_ub", "fz_lb", "fz_ub", "w_pos", "w_rot")) + \
+        tuple("kin." + k for k in KinEnvParams.FIELDS)
+
+    def rollout_backward(self, solver, result, mask, dt, T=None, pd=None, grad_qpos_hist=None,
+                         grad_qvel_hist=None, grad_tau_hist=None, env_params=None,
+                         kin_params=None, want=("qpos0", "qvel0"), stream=None,
+                         workspace="alloc") -> dict:
+        """osc_batch_rollout_backward: the vector-Jacobian product of rollout(..., history=True),
+        one enqueue, no host sync.  `result` is that call's RolloutResult (its histories are the
+        checkpoints), mask / dt / T or pd / env_params / kin_params that call's arguments.  The
+        cotangents grad_qpos_hist (nticks + 1, nenv, nq), grad_qvel_hist (nticks + 1, nenv, nv)
+        and grad_tau_hist (nticks, nenv, nu) are contiguous float64 device tensors or None
+        (= zero); a loss on the final state is a cotangent on the last slab.  `want` names the
+        gradients to compute, out of ROLLOUT_GRADS: "qpos0", "qvel0", "T" (held targets only: the
+        sum over the ticks), "env.<field>" of solver.EnvParams, "kin.<field>" of KinEnvParams.
+        Returns a dict name -> tensor."""
+        from .solver import EnvGrads
+        if (T is None) == (pd is None):
+            raise ValueError("exactly one of T and pd must be given")
+        if result.qpos_hist is None or result.qvel_hist is None or result.status_hist is None:
+            raise ValueError("rollout_backward: the forward call needs history=True")
+        want = tuple(want)
+        for w in want:
+            if w not in self.ROLLOUT_GRADS:
+                raise ValueError(f"rollout_backward: unknown gradient {w!r}")
+        if not want:
+            raise ValueError("rollout_backward: nothing asked for")
+        if pd is not None and "T" in want:
+            raise ValueError("rollout_backward: no grad_T with PD targets")
+        d = solver.dims
+        nticks, nenv = int(result.status_hist.shape[0]), int(result.qpos_hist.shape[1])
+        o = dict(device=self.device, dtype=torch.float64)
+        mask = self._dev(mask, (nenv, d["nc"]), "mask")
+        a = _lib.OscRolloutBackwardArgs()
+        a.nticks, a.dt = nticks, float(dt)
+        keep = [mask]
+        env = env_params is not None or kin_params is not None
+        ep, kp, blocks = self._blocks(solver, env_params, kin_params, nenv) if env else \
+            (None, None, [])
+        keep += blocks
+        if T is not None:
+            T = self._dev(T, (nenv, d["ns"], 6), "T")
+            a.target_mode, a.T = _lib.ROLLOUT_TARGETS_HELD, T.data_ptr()
+            keep.append(T)
+        else:
+            pos_ref, quat_ref, gains = pd
+            pos_ref, quat_ref = (r if isinstance(r, torch.Tensor) else
+                                 np.asarray(r, dtype=np.float64) for r in (pos_ref, quat_ref))
+            per_env = [int(r.ndim == 2) for r in (pos_ref, quat_ref)]
+            pos_ref = self._dev(pos_ref, (nenv, 3) if per_env[0] else (3,), "pos_ref")
+            quat_ref = self._dev(quat_ref, (nenv, 4) if per_env[1] else (4,), "quat_ref")
+            a.target_mode = _lib.ROLLOUT_TARGETS_PD_BASE
+            a.pos_ref, a.pos_ref_per_env = pos_ref.data_ptr(), per_env[0]
+            a.quat_ref, a.quat_ref_per_env = quat_ref.data_ptr(), per_env[1]
+            a.gains[:] = [float(g) for g in gains]
+            keep += [pos_ref, quat_ref]
+        hq = self._grad_tensor(result.qpos_hist, (nticks + 1, nenv, self.nq), "qpos_hist")
+        hv = self._grad_tensor(result.qvel_hist, (nticks + 1, nenv, self.nv), "qvel_hist")
+        hs = self._grad_tensor(result.status_hist, (nticks, nenv), "status_hist", torch.int32)
+        gqh = self._grad_tensor(grad_qpos_hist, (nticks + 1, nenv, self.nq), "grad_qpos_hist")
+        gvh = self._grad_tensor(grad_qvel_hist, (nticks + 1, nenv, self.nv), "grad_qvel_hist")
+        gth = self._grad_tensor(grad_tau_hist, (nticks, nenv, d["nu"]), "grad_tau_hist")
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        a.contact_mask, a.qpos_hist, a.qvel_hist = mask.data_ptr(), hq.data_ptr(), hv.data_ptr()
+        a.status_hist = hs.data_ptr()
+        a.grad_qpos_hist, a.grad_qvel_hist, a.grad_tau_hist = ptr(gqh), ptr(gvh), ptr(gth)
+        out = RolloutGrads()
+        shape = dict(qpos0=(nenv, self.nq), qvel0=(nenv, self.nv), T=(nenv, d["ns"], 6))
+        for w in want:
+            if w in shape:
+                out[w] = torch.empty(shape[w], **o)
+        a.grad_qpos0, a.grad_qvel0, a.grad_T = (ptr(out.get(k)) for k in ("qpos0", "qvel0", "T"))
+        efields = [w[4:] for w in want if w.startswith("env.")]
+        kfields = [w[4:] for w in want if w.startswith("kin.")]
+        if efields:
+            eg = EnvGrads.empty(nenv, d, self.device, efields)
+            ceg = eg.to_struct(nenv, d, self.device)
+            a.env_grads = ctypes.pointer(ceg)
+            keep.append(ceg)
+            out.update({"env." + k: getattr(eg, k) for k in efields})
+        if kfields:
+            kg = KinEnvGrads.empty(nenv, self.nbody, self.nv, self.device, kfields)
+            ckg = _lib.OscKinEnvGrads(**{k: getattr(kg, k).data_ptr() for k in kfields})
+            a.kin_grads = ctypes.pointer(ckg)
+            keep.append(ckg)
+            out.update({"kin." + k: getattr(kg, k) for k in kfields})
+        if isinstance(workspace, str):
+            workspace = torch.empty((max(self.rollout_backward_workspace_bytes(solver, nenv) // 8,
+                                         2),), **o)
+        if workspace is not None:
+            a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
+        s = ctypes.c_void_p(self._stream(stream, self.device))
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().osc_batch_rollout_backward(solver._h, self._h, nenv, ctypes.byref(a),
+                                                       ep, kp, s)
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_rollout_backward", rc)
+        out._keep = keep + [workspace, hq, hv, hs, gqh, gvh, gth]   # alive until the stream is done
+        return out
+
+
+class RolloutGrads(dict):
+    """rollout_backward's result: gradient name -> tensor."""
+    _keep: list | None = None
+
 
 @dataclasses.dataclass
 class RolloutResult:
