@@ -445,6 +445,17 @@ __device__ __forceinline__ void ipm_block(
   // peeled, the warm one of them spilled 10 more SGPRs; and the two-model kernels, PAIR, which
   // hold a second model's body beside Go2's: 3 and 10 more.)
   constexpr bool kPeel = kLean && !PAIR;
+  // The refresh of the rows' residual runs only for envs that go on iterating:
+  // kFreshDone leaves out the envs done on entry, which changes no register of any env; the
+  // peeled kernels (kFreshStop) also the env that stops in the iteration, whose rp then differs
+  // from what it was inside the done env and in no output.  kFlatRecentre: the re-centring's rows
+  // branch-free (Gv_all, selects) in the cold one-wave kernels; the warm ones keep the
+  // exec-masked arm (branch-free they spilled 2 to 6 more SGPRs).  The two-model kernels (PAIR)
+  // keep the parent's body in all three: with the first and the third the mixed workload
+  // measured 2.3 % slower.
+  constexpr bool kFreshDone = !PAIR;
+  constexpr bool kFreshStop = kPeel;
+  constexpr bool kFlatRecentre = SMALL && !WARM && !PAIR;
   if constexpr (REFINE) {
     // the interior point's result for this env (osc_ipm_kernel, W_SOL): y, and the active rows
     // as lambda > s with lambda = q > 0

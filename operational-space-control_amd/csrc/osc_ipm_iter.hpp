@@ -78,7 +78,20 @@
       const bool mine = far && !done && it == (warm ? warm_restart : restart_iter);
       restart = __ballot(mine) != 0;
       if (restart) wave_sync();
-      if (mine) {
+      if constexpr (kFlatRecentre) {
+        if (restart) {   // (wave-uniform; the env's own rows by selects, as the refresh below)
+          double gy[NRL];
+          Gv_all<D>(L, act, sVy, gy);
+#pragma unroll
+          for (int t = 0; t < NRL; ++t) {
+            double sn = fmax(h[t] - gy[t], 0.0) + 1.0;
+            in_vgpr(sn);
+            sn = act[t] ? sn : 1.0;
+            s[t] = mine ? sn : s[t];
+            lam[t] = mine ? (act[t] ? 1.0 : 0.0) : lam[t];
+          }
+        }
+      } else if (mine) {
 #pragma unroll
         for (int t = 0; t < NRL; ++t) {
           const double slack = h[t] - Gv<D>(L, act, sVy, t);
@@ -104,8 +117,23 @@
       mu = row_sum(cs) / fmax(m_act, 1.0);
       const bool fresh = it == 0 || mu <= 1e-6 || restart;
       rd_fresh = fresh || !rd_have;
-      if (__ballot(fresh) != 0) {   // wave-uniform
+      // this iteration's stop test (`done` is still the env's state on entry), formed ahead of the
+      // refresh by the one-wave kernels (the two-wave kernels keep theirs below, where it was:
+      // formed here it cost three of WaLTER's 4 to 8 more bytes of scratch per lane)
+      bool stop = false;
+      if constexpr (SMALL) stop = !done && mu <= eps_run && (!D::WH || rwmax <= P->wheel_tol);
+      // Only an env that goes on iterating needs rp (DESIGN.md §5 "The refresh of the rows'
+      // residual"): a done env's y and s are frozen, so the refresh would give it the bits it
+      // holds (and does, when a wave-mate runs the block); kFreshStop: nor does the env that
+      // stops here, whose rp nothing reads any more.
+      const bool refresh = fresh && (!kFreshDone || (!done && !(kFreshStop && stop)));
+      if (__ballot(refresh) != 0) {   // wave-uniform
+#ifdef OSC_STAMPS
+        st_acc[1] += 1ull << 40;   // refreshes entered, in the top bits of the iteration head's slot
+#endif
         wave_sync();
+        // (the per-row-slot Gv, in the one-wave kernels too: on Gv_all this block, which the Go2
+        // headline now runs once per solve, cost the whole gain of skipping it -- DESIGN.md §5)
 #pragma unroll
         for (int t = 0; t < NRL; ++t) {
           const double r = act[t] ? Gv<D>(L, act, sVy, t) + s[t] - h[t] : 0.0;
@@ -113,7 +141,6 @@
         }
       }
       if constexpr (SMALL) {   // (selects: a lone wave pays a slot per exec-mask instruction)
-        const bool stop = !done && mu <= eps_run && (!D::WH || rwmax <= P->wheel_tol);
         done = done || stop;
         st = stop ? OSC_SOLVE_OK : st;
         it_done = stop ? it : it_done;

@@ -51,6 +51,8 @@ for robot in (sys.argv[2:] or ["unitree_go2", "walter_sr"]):
     raw = np.frombuffer(buf, dtype=np.uint64).reshape(nblk, len(NAMES)).copy()
     rounds = (raw[:, 10] >> np.uint64(40)).astype(np.int64)   # refinement rounds per wave
     raw[:, 10] &= np.uint64((1 << 40) - 1)
+    fresh = (raw[:, 1] >> np.uint64(40)).astype(np.int64)    # iterations that refreshed rp, per wave
+    raw[:, 1] &= np.uint64((1 << 40) - 1)
     a = raw.astype(np.float64)
     it = out.iters.cpu().numpy().reshape(nblk, 4).max(axis=1) + 1   # + init pass
     tot = a.sum(axis=1)
@@ -61,7 +63,10 @@ for robot in (sys.argv[2:] or ["unitree_go2", "walter_sr"]):
                       "mean_wave_iters": float(it.mean()),
                       "cycles_per_wave_iter": float((ipm / it).mean()),
                       "refine_rounds_hist": np.bincount(rounds).tolist(),
+                      "rp_refreshes_per_wave": float(fresh.mean()),
+                      "rp_refreshes_hist": np.bincount(fresh).tolist(),
                       "slowest_wave": {"cycles": float(tot[slow]), "iters": int(it[slow]),
+                                       "rp_refreshes": int(fresh[slow]),
                                        "refine_rounds": int(rounds[slow]),
                                        "refine_cycles": float(a[slow, 10] + a[slow, 11])},
                       "refine_cycles_per_round": float((a[:, 10] + a[:, 11]).sum() /
