@@ -11,8 +11,9 @@
  * host synchronisation and no host <-> device traffic between ticks.
  *
  * THIS IS AN IDEALISED ROLLOUT, NOT A SIMULATOR.  There is no ground and no contact detection:
- * the contact mask is an input, held constant over the rollout, and the contact forces are
- * whatever the QP chose.  It answers "what does this controller do over the next K ticks if its
+ * the contact mask is an input -- held constant over the rollout here, one per tick with
+ * osc_batch_rollout_sched (osc_rollout_schedule.h), which also takes per-tick targets and PD
+ * references -- and the contact forces are whatever the QP chose.  It answers "what does this controller do over the next K ticks if its
  * own model is right?" -- a look-ahead primitive and a source of dynamically consistent tick
  * sequences, not a replacement for a physics engine.
  */

@@ -48,9 +48,10 @@
  * is a three-term series.
  *
  * No atomics: one owning lane per output, sums in index or tick order.  An env's gradients are
- * bitwise reproducible and independent of its row and of the batch around it.  Out of scope:
- * gradients with respect to pos_ref, quat_ref, gains, dt and the mask; the two-model, host-fed and
- * wheel-row entries.
+ * bitwise reproducible and independent of its row and of the batch around it.  Gradients with
+ * respect to pos_ref, quat_ref and the gains, and every tick's own grad_T, are
+ * osc_batch_rollout_backward_sched's (osc_rollout_schedule.h).  Out of scope: gradients with
+ * respect to dt and the mask; the two-model, host-fed and wheel-row entries.
  */
 #ifndef OSC_ROLLOUT_BACKWARD_H_
 #define OSC_ROLLOUT_BACKWARD_H_

@@ -35,6 +35,7 @@
 #include "osc_producers.h"
 #include "osc_qpos.hpp"
 #include "osc_rollout.h"
+#include "osc_rollout_sched.hpp"
 
 namespace {
 
@@ -285,13 +286,13 @@ extern "C" int osc_rollout_workspace_bytes(const osc_model* model, const osc_kin
   return OSC_OK;
 }
 
-namespace {
-
-// osc_batch_rollout (both blocks NULL: every tick through osc_batch_solve_qpos(_warm)) and
+// osc_batch_rollout (both blocks NULL: every tick through osc_batch_solve_qpos(_warm)),
 // osc_batch_rollout_env (every tick through osc_batch_solve_qpos_env, the blocks held constant)
-int rollout(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
-            const osc_rollout_args* args, const osc_env_params* ep, const osc_kin_env_params* kp,
-            void* stream) {
+// and, with a schedule, osc_batch_rollout_sched (osc_rollout_schedule.h): a sequence replaces its
+// held input by tick t's slab pointer, and T_seq is added to the tick's targets in the T slab
+int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
+                     const osc_rollout_args* args, const osc_rollout_schedule* sched,
+                     const osc_env_params* ep, const osc_kin_env_params* kp, void* stream) {
   // ---- every check before the first launch ----
   osc_model_desc d;
   int rc = check_handles(model, kin, &d);
@@ -310,10 +311,21 @@ int rollout(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
   const KinDev& k = kin->host;
   if (pd && (k.jtype[0] != OSC_KIN_JOINT_FREE || k.parent[0] != -1))
     return OSC_ERR_INVALID_ARGUMENT;
+  const osc_rollout_schedule sc = sched ? *sched : osc_rollout_schedule{};
+  if (!pd && (sc.pos_ref_seq || sc.quat_ref_seq)) return OSC_ERR_INVALID_ARGUMENT;
+  for (const double* a : {sc.T_seq, sc.mask_seq, sc.pos_ref_seq, sc.quat_ref_seq})
+    if ((reinterpret_cast<uintptr_t>(a) & 7u) != 0) return OSC_ERR_INVALID_ARGUMENT;
   if (nenv == 0) return OSC_OK;
-  if (!args->qpos || !args->qvel || (d.nc > 0 && !args->contact_mask))
+  // (with a schedule and no tick every sequence is empty, so nothing can stand in for a held
+  // input, and nothing reads one)
+  const bool inputs_read = !sched || args->nticks > 0;
+  if (!args->qpos || !args->qvel) return OSC_ERR_INVALID_ARGUMENT;
+  if (inputs_read && d.nc > 0 && !args->contact_mask && !sc.mask_seq)
     return OSC_ERR_INVALID_ARGUMENT;
-  if (pd ? (!args->pos_ref || !args->quat_ref) : !args->T) return OSC_ERR_INVALID_ARGUMENT;
+  if (inputs_read &&
+      (pd ? ((!args->pos_ref && !sc.pos_ref_seq) || (!args->quat_ref && !sc.quat_ref_seq))
+          : (!args->T && !sc.T_seq)))
+    return OSC_ERR_INVALID_ARGUMENT;
   if ((reinterpret_cast<uintptr_t>(args->workspace) & 15u) != 0) return OSC_ERR_INVALID_ARGUMENT;
   const RolloutWorkspace L(model, kin, d, nenv);
   if (L.rc != OSC_OK) return L.rc;
@@ -363,25 +375,41 @@ int rollout(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
   // ---- ticks ----
   for (int32_t t = 0; t < nticks && rc == OSC_OK; ++t) {
     const double* T = args->T;
+    const double* mask = sc.mask_seq ? sc.mask_seq + n * d.nc * t : args->contact_mask;
     if (pd) {
+      const double* pos_ref =
+          sc.pos_ref_seq ? sc.pos_ref_seq + (args->pos_ref_per_env ? n * 3 : 3) * t : args->pos_ref;
+      const double* quat_ref = sc.quat_ref_seq
+                                   ? sc.quat_ref_seq + (args->quat_ref_per_env ? n * 4 : 4) * t
+                                   : args->quat_ref;
       rc = osc_pd_base_targets(nenv, d.ns, dptr(L.bpos), dptr(L.bquat), dptr(L.blin), dptr(L.bang),
-                               args->pos_ref, args->pos_ref_per_env, args->quat_ref,
-                               args->quat_ref_per_env, args->gains, Tbuf, stream);
+                               pos_ref, args->pos_ref_per_env, quat_ref, args->quat_ref_per_env,
+                               args->gains, Tbuf, stream);
       T = Tbuf;
       if (rc != OSC_OK) break;
     }
+    if (sc.T_seq) {   // T_t = T + T_seq[t]; nothing to add to: the slab itself
+      const double* add = sc.T_seq + n * d.ns * 6 * t;
+      if (T) {
+        rc = osc::launch_sched_add(T, add, Tbuf, static_cast<long long>(n) * d.ns * 6, s);
+        T = Tbuf;
+        if (rc != OSC_OK) break;
+      } else {
+        T = add;
+      }
+    }
     int32_t* status = args->status_hist ? args->status_hist + n * t : status_ws;
     if (env)
-      rc = osc_batch_solve_qpos_env(model, kin, nenv, args->qpos, args->qvel, T, args->contact_mask,
+      rc = osc_batch_solve_qpos_env(model, kin, nenv, args->qpos, args->qvel, T, mask,
                                     ep, kp, nullptr, tau, x, status, nullptr,
                                     warm ? wstate : nullptr, warm ? L.warm_bytes : 0, base + L.qp,
                                     L.qp_bytes, stream);
     else
       rc = warm ? osc_batch_solve_qpos_warm(model, kin, nenv, args->qpos, args->qvel, T,
-                                            args->contact_mask, tau, x, status, nullptr, wstate,
+                                            mask, tau, x, status, nullptr, wstate,
                                             L.warm_bytes, base + L.qp, L.qp_bytes, stream)
                 : osc_batch_solve_qpos(model, kin, nenv, args->qpos, args->qvel, T,
-                                       args->contact_mask, tau, x, status, nullptr, base + L.qp,
+                                       mask, tau, x, status, nullptr, base + L.qp,
                                        L.qp_bytes, stream);
     if (rc != OSC_OK) break;
     StepArgs a = step_args(kin, nenv);
@@ -409,11 +437,9 @@ int rollout(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
   return rc;
 }
 
-}  // namespace
-
 extern "C" int osc_batch_rollout(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
                                  const osc_rollout_args* args, void* stream) {
-  return rollout(model, kin, nenv, args, nullptr, nullptr, stream);
+  return osc::rollout_run(model, kin, nenv, args, nullptr, nullptr, nullptr, stream);
 }
 
 // (the tick's workspace is osc_qpos_env_workspace_bytes, which is osc_qpos_workspace_bytes: one
@@ -426,5 +452,5 @@ extern "C" int osc_rollout_env_workspace_bytes(const osc_model* model, const osc
 extern "C" int osc_batch_rollout_env(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
                                      const osc_rollout_args* args, const osc_env_params* env_params,
                                      const osc_kin_env_params* kin_params, void* stream) {
-  return rollout(model, kin, nenv, args, env_params, kin_params, stream);
+  return osc::rollout_run(model, kin, nenv, args, nullptr, env_params, kin_params, stream);
 }

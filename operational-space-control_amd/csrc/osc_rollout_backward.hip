@@ -30,6 +30,7 @@
 #include "osc_producers.h"
 #include "osc_qpos.hpp"
 #include "osc_rollout_backward.h"
+#include "osc_rollout_sched.hpp"
 
 namespace {
 
@@ -43,6 +44,7 @@ constexpr int kBlock = 256;
 constexpr int kEnvPerBlock = 16;
 constexpr int kMaxNq = OSC_KIN_MAX_DOFS + OSC_KIN_MAX_BODIES;   // as osc_rollout.hip
 constexpr int kMaxAcc = 11;   // grad_T, seven osc_env_grads fields, three osc_kin_env_grads fields
+static_assert(osc::kSchedMaxAcc == kMaxAcc, "the scheduled combine holds the same sums");
 
 // a (x) b, quaternions (w, x, y, z)
 __device__ __forceinline__ void quat_mul(const double* a, const double* b, double* o) {
@@ -539,6 +541,17 @@ extern "C" int osc_batch_rollout_backward(const osc_model* model, const osc_kin_
                                           int32_t nenv, const osc_rollout_backward_args* args,
                                           const osc_env_params* ep, const osc_kin_env_params* kp,
                                           void* stream) {
+  return osc::rollout_backward_run(model, kin, nenv, args, nullptr, nullptr, ep, kp, stream);
+}
+
+// osc_batch_rollout_backward (sched and sgrads NULL) and osc_batch_rollout_backward_sched
+// (osc_rollout_schedule.h): the recompute of tick t on the schedule's slabs, and the scheduled
+// combine kernel in place of this unit's whenever a schedule or one of its gradients is given
+int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
+                              const osc_rollout_backward_args* args,
+                              const osc_rollout_schedule* sched,
+                              const osc_rollout_schedule_grads* sgrads, const osc_env_params* ep,
+                              const osc_kin_env_params* kp, void* stream) {
   // ---- every check before the first launch ----
   osc_model_desc d;
   int rc = check_handles(model, kin, &d);
@@ -581,7 +594,25 @@ extern "C" int osc_batch_rollout_backward(const osc_model* model, const osc_kin_
     for (const double* a : {kp->mass_scale, kp->com_offset, kp->armature_scale})
       if (!aligned8(a)) return OSC_ERR_INVALID_ARGUMENT;
   if (pd && args->grad_T) return OSC_ERR_INVALID_ARGUMENT;
-  if (!args->grad_qpos0 && !args->grad_qvel0 && !args->grad_T && !any_eg && !any_kg)
+  const osc_rollout_schedule sc = sched ? *sched : osc_rollout_schedule{};
+  const osc_rollout_schedule_grads sg = sgrads ? *sgrads : osc_rollout_schedule_grads{};
+  const bool any_sg = sg.grad_T_seq || sg.grad_pos_ref || sg.grad_quat_ref ||
+                      sg.grad_pos_ref_seq || sg.grad_quat_ref_seq || sg.grad_gains;
+  const bool scheduled = any_sg || sc.T_seq || sc.mask_seq || sc.pos_ref_seq || sc.quat_ref_seq;
+  if (!pd && (sc.pos_ref_seq || sc.quat_ref_seq || sg.grad_pos_ref || sg.grad_quat_ref ||
+              sg.grad_pos_ref_seq || sg.grad_quat_ref_seq || sg.grad_gains))
+    return OSC_ERR_INVALID_ARGUMENT;
+  if ((sg.grad_pos_ref_seq && !sc.pos_ref_seq) || (sg.grad_quat_ref_seq && !sc.quat_ref_seq) ||
+      (sg.grad_pos_ref && sc.pos_ref_seq) || (sg.grad_quat_ref && sc.quat_ref_seq))
+    return OSC_ERR_INVALID_ARGUMENT;
+  for (const void* p :
+       {static_cast<const void*>(sc.T_seq), static_cast<const void*>(sc.mask_seq),
+        static_cast<const void*>(sc.pos_ref_seq), static_cast<const void*>(sc.quat_ref_seq),
+        static_cast<const void*>(sg.grad_T_seq), static_cast<const void*>(sg.grad_pos_ref),
+        static_cast<const void*>(sg.grad_quat_ref), static_cast<const void*>(sg.grad_pos_ref_seq),
+        static_cast<const void*>(sg.grad_quat_ref_seq), static_cast<const void*>(sg.grad_gains)})
+    if (!aligned8(p)) return OSC_ERR_INVALID_ARGUMENT;
+  if (!args->grad_qpos0 && !args->grad_qvel0 && !args->grad_T && !any_eg && !any_kg && !any_sg)
     return OSC_ERR_INVALID_ARGUMENT;
   for (const void* p :
        {static_cast<const void*>(args->T), static_cast<const void*>(args->pos_ref),
@@ -595,8 +626,14 @@ extern "C" int osc_batch_rollout_backward(const osc_model* model, const osc_kin_
   if ((reinterpret_cast<uintptr_t>(args->status_hist) & 3u) != 0) return OSC_ERR_INVALID_ARGUMENT;
   if (nenv == 0) return OSC_OK;
   const int32_t nticks = args->nticks;
-  if (d.nc > 0 && !args->contact_mask) return OSC_ERR_INVALID_ARGUMENT;
-  if (pd ? (!args->pos_ref || !args->quat_ref) : !args->T) return OSC_ERR_INVALID_ARGUMENT;
+  // (as the forward: with a schedule and no tick nothing reads a held input or a sequence)
+  const bool inputs_read = !sched || nticks > 0;
+  if (inputs_read && d.nc > 0 && !args->contact_mask && !sc.mask_seq)
+    return OSC_ERR_INVALID_ARGUMENT;
+  if (inputs_read &&
+      (pd ? ((!args->pos_ref && !sc.pos_ref_seq) || (!args->quat_ref && !sc.quat_ref_seq))
+          : (!args->T && !sc.T_seq)))
+    return OSC_ERR_INVALID_ARGUMENT;
   if (nticks > 0 && (!args->qpos_hist || !args->qvel_hist || !args->status_hist))
     return OSC_ERR_INVALID_ARGUMENT;
   if ((reinterpret_cast<uintptr_t>(args->workspace) & 15u) != 0) return OSC_ERR_INVALID_ARGUMENT;
@@ -618,6 +655,9 @@ extern "C" int osc_batch_rollout_backward(const osc_model* model, const osc_kin_
     if (eg_out[i]) rc = ok(hipMemsetAsync(eg_out[i], 0, dbl * n * L.eg_cnt[i], s));
   for (int i = 0; i < kKinFields && rc == OSC_OK; ++i)
     if (kg_out[i]) rc = ok(hipMemsetAsync(kg_out[i], 0, dbl * n * L.kg_cnt[i], s));
+  if (rc == OSC_OK && sg.grad_pos_ref) rc = ok(hipMemsetAsync(sg.grad_pos_ref, 0, dbl * n * 3, s));
+  if (rc == OSC_OK && sg.grad_quat_ref) rc = ok(hipMemsetAsync(sg.grad_quat_ref, 0, dbl * n * 4, s));
+  if (rc == OSC_OK && sg.grad_gains) rc = ok(hipMemsetAsync(sg.grad_gains, 0, dbl * n * 4, s));
   if (rc != OSC_OK) return rc;
 
   auto seed = [&](double* out, const double* hist, size_t row) {   // slab nticks' cotangent
@@ -644,7 +684,7 @@ extern "C" int osc_batch_rollout_backward(const osc_model* model, const osc_kin_
   double *M = dptr(L.M), *C = dptr(L.C), *J = dptr(L.J), *b = dptr(L.b), *x = dptr(L.x);
   double *gq = dptr(L.gq), *gv = dptr(L.gv);
   int32_t* status = reinterpret_cast<int32_t*>(base + L.status);
-  const bool want_gT = pd || args->grad_T != nullptr;
+  const bool want_gT = pd || args->grad_T != nullptr || sg.grad_T_seq != nullptr;
 
   // this tick's parameter gradients land in the workspace, the combine kernel adds them on
   osc_env_grads eg_tick{};
@@ -676,18 +716,34 @@ extern "C" int osc_batch_rollout_backward(const osc_model* model, const osc_kin_
             : osc_batch_kinematics(kin, nenv, qpos, qvel, M, C, J, b, nullptr, stream);
     if (rc != OSC_OK) break;
     const double* T = args->T;
+    const double* mask = sc.mask_seq ? sc.mask_seq + n * d.nc * t : args->contact_mask;
+    const double* pos_ref =
+        sc.pos_ref_seq ? sc.pos_ref_seq + (args->pos_ref_per_env ? n * 3 : 3) * t : args->pos_ref;
+    const double* quat_ref =
+        sc.quat_ref_seq ? sc.quat_ref_seq + (args->quat_ref_per_env ? n * 4 : 4) * t
+                        : args->quat_ref;
     if (pd) {
       rc = osc_pd_base_targets(nenv, d.ns, dptr(L.bpos), dptr(L.bquat), dptr(L.blin), dptr(L.bang),
-                               args->pos_ref, args->pos_ref_per_env, args->quat_ref,
-                               args->quat_ref_per_env, args->gains, dptr(L.T), stream);
+                               pos_ref, args->pos_ref_per_env, quat_ref, args->quat_ref_per_env,
+                               args->gains, dptr(L.T), stream);
       T = dptr(L.T);
       if (rc != OSC_OK) break;
     }
+    if (sc.T_seq) {   // as the forward: T_t = T + T_seq[t], or the slab itself
+      const double* add = sc.T_seq + n * s6 * t;
+      if (T) {
+        rc = osc::launch_sched_add(T, add, dptr(L.T), static_cast<long long>(n * s6), s);
+        T = dptr(L.T);
+        if (rc != OSC_OK) break;
+      } else {
+        T = add;
+      }
+    }
     osc_solve_extras ex{};
     ex.y = dptr(L.y);
-    rc = ep ? osc_batch_solve_env(model, nenv, M, C, J, b, T, args->contact_mask, ep, &ex,
+    rc = ep ? osc_batch_solve_env(model, nenv, M, C, J, b, T, mask, ep, &ex,
                                   dptr(L.tau), x, status, nullptr, base + L.qp, L.qp_bytes, stream)
-            : osc_batch_solve_ex(model, nenv, M, C, J, b, T, args->contact_mask, &ex, dptr(L.tau),
+            : osc_batch_solve_ex(model, nenv, M, C, J, b, T, mask, &ex, dptr(L.tau),
                                  x, status, nullptr, base + L.qp, L.qp_bytes, stream);
     if (rc != OSC_OK) break;
     // ---- the step's adjoint: grad_x, and the direct part of slab t's adjoints in place ----
@@ -716,12 +772,12 @@ extern "C" int osc_batch_rollout_backward(const osc_model* model, const osc_kin_
     if (rc != OSC_OK) break;
     // ---- the solve's backward, then the kinematics' ----
     double* gT = want_gT ? dptr(L.gT) : nullptr;
-    rc = env_bwd ? osc_batch_solve_backward_env(model, nenv, M, J, b, T, args->contact_mask, ep, x,
+    rc = env_bwd ? osc_batch_solve_backward_env(model, nenv, M, J, b, T, mask, ep, x,
                                                 dptr(L.y), status, dptr(L.gx), dptr(L.gM),
                                                 dptr(L.gC), dptr(L.gJ), nullptr, gT, dptr(L.gb),
                                                 any_eg ? &eg_tick : nullptr, base + L.qp,
                                                 L.qp_bytes, stream)
-                 : osc_batch_solve_backward_data(model, nenv, M, J, b, T, args->contact_mask, x,
+                 : osc_batch_solve_backward_data(model, nenv, M, J, b, T, mask, x,
                                                  dptr(L.y), status, dptr(L.gx), dptr(L.gM),
                                                  dptr(L.gC), dptr(L.gJ), nullptr, gT, dptr(L.gb),
                                                  base + L.qp, L.qp_bytes, stream);
@@ -731,6 +787,59 @@ extern "C" int osc_batch_rollout_backward(const osc_model* model, const osc_kin_
                                        any_kg ? &kg_tick : nullptr, stream);
     if (rc != OSC_OK) break;
     // ---- combine: slab t's adjoints, the tick-ordered sums, the next tick's base state ----
+    if (scheduled) {   // the same, and the schedule's outputs, in one launch
+      osc::SchedCombineArgs c{};
+      c.nenv = nenv;
+      c.nq = k.nq;
+      c.nv = k.nv;
+      c.ns = d.ns;
+      c.gq = gq;
+      c.gv = gv;
+      c.kq = dptr(L.kq);
+      c.kv = dptr(L.kv);
+      c.hq = args->grad_qpos_hist ? args->grad_qpos_hist + n * nq * t : nullptr;
+      c.hv = args->grad_qvel_hist ? args->grad_qvel_hist + n * nv * t : nullptr;
+      c.gT = gT;
+      if (pd) {
+        c.pd = 1;
+        c.pos_ref = pos_ref;
+        c.pos_ref_stride = args->pos_ref_per_env ? 3 : 0;
+        c.quat_ref = quat_ref;
+        c.quat_ref_stride = args->quat_ref_per_env ? 4 : 0;
+        c.kp_lin = args->gains[0];
+        c.kd_lin = args->gains[1];
+        c.kp_ang = args->gains[2];
+        c.kd_ang = args->gains[3];
+        if (t > 0) {
+          c.pack_qpos = args->qpos_hist + n * nq * (t - 1);
+          c.pack_qvel = args->qvel_hist + n * nv * (t - 1);
+          c.bpos = dptr(L.bpos);
+          c.bquat = dptr(L.bquat);
+          c.blin = dptr(L.blin);
+          c.bang = dptr(L.bang);
+        }
+        c.qpos = qpos;
+        c.qvel = qvel;
+        c.gpos_ref = sg.grad_pos_ref_seq ? sg.grad_pos_ref_seq + n * 3 * t : sg.grad_pos_ref;
+        c.pos_ref_add = sg.grad_pos_ref_seq ? 0 : 1;
+        c.gquat_ref = sg.grad_quat_ref_seq ? sg.grad_quat_ref_seq + n * 4 * t : sg.grad_quat_ref;
+        c.quat_ref_add = sg.grad_quat_ref_seq ? 0 : 1;
+        c.ggains = sg.grad_gains;
+      }
+      c.gT_slab = sg.grad_T_seq ? sg.grad_T_seq + n * s6 * t : nullptr;
+      if (args->grad_T)
+        c.acc[c.nacc++] = osc::SchedAcc{args->grad_T, gT, static_cast<int32_t>(s6)};
+      for (int i = 0; i < kEnvFields; ++i)
+        if (eg_out[i])
+          c.acc[c.nacc++] =
+              osc::SchedAcc{eg_out[i], dptr(L.eg[i]), static_cast<int32_t>(L.eg_cnt[i])};
+      for (int i = 0; i < kKinFields; ++i)
+        if (kg_out[i])
+          c.acc[c.nacc++] =
+              osc::SchedAcc{kg_out[i], dptr(L.kg[i]), static_cast<int32_t>(L.kg_cnt[i])};
+      rc = osc::launch_sched_combine(c, s);
+      continue;
+    }
     CombineArgs c{};
     c.nenv = nenv;
     c.nq = k.nq;

@@ -73,6 +73,10 @@ KIN_BACKWARD_SYMBOLS = ("osc_batch_kinematics_backward",)
 # tests/test_rollout_backward_ref.py pins this list to that header's declarations.
 ROLLOUT_BACKWARD_SYMBOLS = ("osc_batch_integrate_backward", "osc_pd_base_targets_backward",
                             "osc_rollout_backward_workspace_bytes", "osc_batch_rollout_backward")
+# include/osc_rollout_schedule.h (per-tick targets, masks and references, and their gradients),
+# apart likewise; tests/test_rollout_schedule_ref.py pins this list to that header's declarations.
+ROLLOUT_SCHEDULE_SYMBOLS = ("osc_batch_rollout_sched", "osc_pd_base_targets_backward_params",
+                            "osc_batch_rollout_backward_sched")
 
 OSC_KIN_MAX_BODIES = 16
 OSC_KIN_MAX_DOFS = 32
@@ -230,6 +234,18 @@ class OscRolloutBackwardArgs(ctypes.Structure):
          ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
+class OscRolloutSchedule(ctypes.Structure):
+    """osc_rollout_schedule (include/osc_rollout_schedule.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("T_seq", "mask_seq", "pos_ref_seq", "quat_ref_seq")]
+
+
+class OscRolloutScheduleGrads(ctypes.Structure):
+    """osc_rollout_schedule_grads (include/osc_rollout_schedule.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("grad_T_seq", "grad_pos_ref", "grad_quat_ref",
+                                                "grad_pos_ref_seq", "grad_quat_ref_seq",
+                                                "grad_gains")]
+
+
 FEED_QP, FEED_JOINT_STATES, FEED_WARM = 0, 1, 1
 
 
@@ -381,6 +397,16 @@ def lib() -> ctypes.CDLL:
     L.osc_batch_rollout_backward.argtypes = [vp, vp, i32, ctypes.POINTER(OscRolloutBackwardArgs),
                                              ep, kep, vp]
     for name in ROLLOUT_BACKWARD_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
+    scp, sgp = ctypes.POINTER(OscRolloutSchedule), ctypes.POINTER(OscRolloutScheduleGrads)
+    L.osc_batch_rollout_sched.argtypes = [vp, vp, i32, ctypes.POINTER(OscRolloutArgs), scp, ep,
+                                          kep, vp]
+    L.osc_pd_base_targets_backward_params.argtypes = [i32, i32] + [vp] * 5 + [i32, vp, i32] + \
+        [vp] * 6
+    L.osc_batch_rollout_backward_sched.argtypes = [vp, vp, i32,
+                                                   ctypes.POINTER(OscRolloutBackwardArgs), scp,
+                                                   sgp, ep, kep, vp]
+    for name in ROLLOUT_SCHEDULE_SYMBOLS:
         getattr(L, name).restype = ctypes.c_int
     L.osc_batch_solve_backward.argtypes = [vp, i32] + [vp] * 8 + [ctypes.c_size_t, vp]
     L.osc_batch_solve_backward.restype = ctypes.c_int

@@ -316,30 +316,91 @@ class _Rollout(torch.autograd.Function):
         return none[:_Rollout.NFIXED] + tuple(g.get(n) for n in names)
 
 
+class _RolloutSched(torch.autograd.Function):
+    """KinematicsBatch.rollout(..., schedule=) with histories (osc_batch_rollout_sched and its
+    backward, include/osc_rollout_schedule.h); qpos, qvel, the held T, schedule.T, the two PD
+    references (held, or the schedule's: seq_refs), the gains and the parameter fields follow as
+    explicit inputs (a tensor, or None / a plain value where no gradient is wanted)."""
+
+    NFIXED = 11   # solver .. pd_mode
+
+    @staticmethod
+    def _call(sched_mask, seq_refs, pd_mode, T, sched_T, pos_ref, quat_ref, gains):
+        from .kinematics import RolloutSchedule
+        schedule = RolloutSchedule(T=sched_T, mask=sched_mask,
+                                   pos_ref=pos_ref if seq_refs[0] else None,
+                                   quat_ref=quat_ref if seq_refs[1] else None)
+        pd = None
+        if pd_mode:
+            g = gains.detach().cpu().tolist() if isinstance(gains, torch.Tensor) else gains
+            pd = (None if seq_refs[0] else pos_ref, None if seq_refs[1] else quat_ref, g)
+        return schedule, pd
+
+    @staticmethod
+    def forward(ctx, solver, kin, mask, nticks, dt, warm, env_params, kin_params, sched_mask,
+                seq_refs, pd_mode, qpos, qvel, T, sched_T, pos_ref, quat_ref, gains, *fields):
+        schedule, pd = _RolloutSched._call(sched_mask, seq_refs, pd_mode, T, sched_T, pos_ref,
+                                           quat_ref, gains)
+        res = kin.rollout(solver, qpos, qvel, mask, nticks, dt, T=T, pd=pd, warm=warm,
+                          history=True, env_params=env_params, kin_params=kin_params,
+                          schedule=schedule)
+        ctx.call = (solver, kin, mask, dt, pd, env_params, kin_params, T, schedule, seq_refs)
+        ctx.res = res
+        ctx.mark_non_differentiable(res.status_hist)
+        return res.qpos_hist, res.qvel_hist, res.tau_hist, res.status_hist
+
+    @staticmethod
+    def backward(ctx, gq, gv, gt, _grad_status):
+        solver, kin, mask, dt, pd, env_params, kin_params, T, schedule, seq_refs = ctx.call
+        names = ("qpos0", "qvel0", "T", "T_seq", "pos_ref_seq" if seq_refs[0] else "pos_ref",
+                 "quat_ref_seq" if seq_refs[1] else "quat_ref", "gains") + \
+            tuple("env." + k for k in EnvParams.FIELDS) + \
+            tuple("kin." + k for k in KinEnvParams.FIELDS)
+        need = ctx.needs_input_grad[_RolloutSched.NFIXED:]
+        want = tuple(n for n, w in zip(names, need) if w)
+        none = (None,) * (_RolloutSched.NFIXED + len(names))
+        if not want or all(g is None for g in (gq, gv, gt)):
+            return none
+        cot = [None if g is None else g.to(dtype=torch.float64).contiguous() for g in (gq, gv, gt)]
+        g = kin.rollout_backward(solver, ctx.res, mask, dt, T=T, pd=pd, grad_qpos_hist=cot[0],
+                                 grad_qvel_hist=cot[1], grad_tau_hist=cot[2],
+                                 env_params=env_params, kin_params=kin_params, want=want,
+                                 schedule=schedule)
+        return none[:_RolloutSched.NFIXED] + tuple(g.get(n) for n in names)
+
+
 def rollout_differentiable(solver: OSCBatchSolver, kin: KinematicsBatch, qpos, qvel, mask,
                            nticks: int, dt: float, T=None, pd=None, warm: bool = True,
-                           env_params=None, kin_params=None):
+                           env_params=None, kin_params=None, schedule=None):
     """(qpos_hist, qvel_hist, tau_hist, status_hist) of the closed-loop rollout
-    (KinematicsBatch.rollout(..., history=True): its forward values, bitwise), differentiable with
-    respect to qpos, qvel, a held T and the tensor fields of env_params (a solver.EnvParams) and
-    kin_params (a KinEnvParams) that require a gradient -- float64, on kin's device, ValueError
-    otherwise; a numpy field, or a tensor without requires_grad, gets none.  Exactly one of T
-    (held targets) and pd = (pos_ref, quat_ref, gains); the PD references and gains, dt and the
-    mask get no gradient.  The backward is one call (osc_batch_rollout_backward,
-    include/osc_rollout_backward.h) that recomputes the ticks from the histories and fills only
-    what autograd asks for; a loss may touch any slab of the three histories.  The gradient with
-    respect to qpos is with respect to the raw nq coordinates."""
+    (KinematicsBatch.rollout(..., history=True, schedule=...): its forward values, bitwise),
+    differentiable with respect to qpos, qvel, a held T and the tensor fields of env_params (a
+    solver.EnvParams) and kin_params (a KinEnvParams) that require a gradient -- float64, on kin's
+    device, ValueError otherwise; a numpy field, or a tensor without requires_grad, gets none.
+    Without a schedule exactly one of T (held targets) and pd = (pos_ref, quat_ref, gains).
+    With schedule (a kinematics.RolloutSchedule: inputs that change over the ticks) gradients also
+    flow to schedule.T (every tick's target gradient: a target sequence can be optimised),
+    schedule.pos_ref and schedule.quat_ref.  The held PD references get a gradient too, and so do
+    the gains when they are passed as a float64 tensor of 4 on kin's device (their values are read
+    on the host: one synchronisation).  dt and the mask, held or scheduled, get no gradient.
+    The backward is one call (osc_batch_rollout_backward, include/osc_rollout_backward.h, or
+    osc_batch_rollout_backward_sched, include/osc_rollout_schedule.h) that recomputes the ticks
+    from the histories and fills only what autograd asks for; a loss may touch any slab of the
+    three histories.  The gradient with respect to qpos is with respect to the raw nq
+    coordinates."""
     if env_params is not None and not isinstance(env_params, EnvParams):
         raise TypeError("rollout_differentiable: env_params must be an EnvParams")
     if kin_params is not None and not isinstance(kin_params, KinEnvParams):
         raise TypeError("rollout_differentiable: kin_params must be a KinEnvParams")
-    if (T is None) == (pd is None):
+    grad_t = lambda r: isinstance(r, torch.Tensor) and r.requires_grad
+    sched = schedule is not None or (pd is not None and any(grad_t(r) for r in pd))
+    if sched:
+        if T is not None and pd is not None:
+            raise ValueError("rollout_differentiable: at most one of T and pd may be given")
+        if T is None and pd is None and (schedule is None or schedule.T is None):
+            raise ValueError("rollout_differentiable: one of T, pd and schedule.T must be given")
+    elif (T is None) == (pd is None):
         raise ValueError("rollout_differentiable: exactly one of T and pd must be given")
-    if pd is not None:
-        for r in pd[:2]:
-            if isinstance(r, torch.Tensor) and r.requires_grad:
-                raise ValueError("rollout_differentiable: no gradient with respect to the PD "
-                                 "references")
     d = solver.dims
     nenv = int(qpos.shape[0])
     qpos = kin._dev(qpos, (nenv, kin.nq), "qpos")
@@ -358,5 +419,26 @@ def rollout_differentiable(solver: OSCBatchSolver, kin: KinematicsBatch, qpos, q
                 fields.append(a)
             else:
                 fields.append(None)
+    if sched:
+        from .kinematics import RolloutSchedule
+        sc = schedule if schedule is not None else RolloutSchedule()
+        pos_ref, quat_ref, gains = pd if pd is not None else (None, None, None)
+        seq_refs = (sc.pos_ref is not None, sc.quat_ref is not None)
+        refs = [sc.pos_ref if seq_refs[0] else pos_ref, sc.quat_ref if seq_refs[1] else quat_ref]
+        for i, r in enumerate(refs):
+            if grad_t(r) and (r.dtype != torch.float64 or r.device != kin.device):
+                raise ValueError("rollout_differentiable: a PD reference that requires a gradient "
+                                 f"must be float64 on {kin.device}")
+        if grad_t(gains) and (gains.dtype != torch.float64 or gains.device != kin.device or
+                              tuple(gains.shape) != (4,)):
+            raise ValueError("rollout_differentiable: gains that require a gradient must be a "
+                             f"float64 tensor of 4 on {kin.device}")
+        sT = sc.T
+        if grad_t(sT) and (sT.dtype != torch.float64 or sT.device != kin.device):
+            raise ValueError("rollout_differentiable: schedule.T requires a gradient and must be "
+                             f"float64 on {kin.device}")
+        return _RolloutSched.apply(solver, kin, mask, int(nticks), float(dt), bool(warm),
+                                   env_params, kin_params, sc.mask, seq_refs, pd is not None,
+                                   qpos, qvel, T, sT, refs[0], refs[1], gains, *fields)
     return _Rollout.apply(solver, kin, mask, int(nticks), float(dt), pd, bool(warm), env_params,
                           kin_params, qpos, qvel, T, *fields)

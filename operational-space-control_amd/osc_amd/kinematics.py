@@ -421,12 +421,69 @@ class KinematicsBatch:
             raise _lib.OSCError(name, rc)
         return nb.value
 
+    def _schedule(self, schedule, solver, nenv, nticks, pd_mode):
+        """(osc_rollout_schedule, tensors name -> device tensor, per_env name -> 0 / 1) of a
+        RolloutSchedule, its shapes validated against nticks."""
+        d = solver.dims
+        if not isinstance(schedule, RolloutSchedule):
+            raise TypeError("schedule must be a RolloutSchedule")
+        c, t, per_env = _lib.OscRolloutSchedule(), {}, {}
+        if schedule.T is not None:
+            t["T"] = self._dev(schedule.T, (nticks, nenv, d["ns"], 6), "schedule.T")
+            c.T_seq = t["T"].data_ptr()
+        if schedule.mask is not None:
+            t["mask"] = self._dev(schedule.mask, (nticks, nenv, d["nc"]), "schedule.mask")
+            c.mask_seq = t["mask"].data_ptr()
+        for name, w in (("pos_ref", 3), ("quat_ref", 4)):
+            r = getattr(schedule, name)
+            if r is None:
+                continue
+            if not pd_mode:
+                raise ValueError(f"schedule.{name}: a reference sequence needs PD targets (pd=)")
+            r = r if isinstance(r, torch.Tensor) else np.asarray(r, dtype=np.float64)
+            per_env[name] = int(r.ndim == 3)
+            t[name] = self._dev(r, (nticks, nenv, w) if per_env[name] else (nticks, w),
+                                "schedule." + name)
+            setattr(c, name + "_seq", t[name].data_ptr())
+        return c, t, per_env
+
+    def _pd_args(self, a, pd, nenv, per_env_seq):
+        """Fill a's PD fields from pd = (pos_ref, quat_ref, gains); a reference may be None when
+        the schedule carries it (per_env_seq).  Returns the reference tensors (None = absent)."""
+        pos_ref, quat_ref, gains = pd
+        refs = {}
+        for name, r, w in (("pos_ref", pos_ref, 3), ("quat_ref", quat_ref, 4)):
+            if r is None:
+                if name not in per_env_seq:
+                    raise ValueError(f"{name}: None needs a schedule that carries it")
+                setattr(a, name + "_per_env", per_env_seq[name])
+                refs[name] = None
+                continue
+            r = r if isinstance(r, torch.Tensor) else np.asarray(r, dtype=np.float64)
+            per = int(r.ndim == 2)
+            if name in per_env_seq:     # the sequence's layout rules; it is what every tick reads
+                per = per_env_seq[name]
+            r = self._dev(r, (nenv, w) if per else (w,), name)
+            setattr(a, name, r.data_ptr())
+            setattr(a, name + "_per_env", per)
+            refs[name] = r
+        a.target_mode = _lib.ROLLOUT_TARGETS_PD_BASE
+        a.gains[:] = [float(g) for g in gains]
+        return refs
+
     def rollout(self, solver, qpos, qvel, mask, nticks: int, dt: float, T=None, pd=None,
                 warm: bool = True, history: bool = False, stream=None,
-                workspace="alloc", env_params=None, kin_params=None) -> "RolloutResult":
+                workspace="alloc", env_params=None, kin_params=None,
+                schedule=None) -> "RolloutResult":
         """osc_batch_rollout: nticks ticks of kinematics -> targets -> solve -> step on the
         device, one enqueue, no host sync.  An idealised rollout over the controller's model, not
-        a simulator: no ground, no contact detection, `mask` held constant.
+        a simulator: no ground, no contact detection; `mask` is an input, held constant unless
+        the schedule carries one per tick.
+        schedule (a RolloutSchedule): osc_batch_rollout_sched, inputs that change over the ticks.
+        schedule.T (nticks, nenv, ns, 6) is ADDED to the tick's targets (the held T, which may
+        then be None = 0, or the PD targets: a feed-forward); schedule.mask (nticks, nenv, nc)
+        and schedule.pos_ref / quat_ref ((nticks, 3 | 4) shared or (nticks, nenv, 3 | 4) per env)
+        replace the held ones, which may then be None (pd = (None, None, gains)).
         Exactly one of T (nenv, ns, 6), targets held over the rollout, and pd = (pos_ref,
         quat_ref, gains), osc_pd_base_targets of the current state every tick (references (3,) /
         (4,) shared or (nenv, 3) / (nenv, 4) per env; gains (kp_lin, kd_lin, kp_ang, kd_ang)).
@@ -435,6 +492,9 @@ class KinematicsBatch:
         stream-ordered scratch, or a float64 device tensor.
         env_params (a solver.EnvParams) / kin_params (a KinEnvParams): osc_batch_rollout_env, both
         blocks held constant over the rollout; an env with invalid parameters stays frozen."""
+        if schedule is not None:
+            return self._rollout_sched(solver, qpos, qvel, mask, nticks, dt, T, pd, warm, history,
+                                       stream, workspace, env_params, kin_params, schedule)
         if (T is None) == (pd is None):
             raise ValueError("exactly one of T and pd must be given")
         d = solver.dims
@@ -492,6 +552,67 @@ class KinematicsBatch:
                 rc = _lib.lib().osc_batch_rollout(solver._h, self._h, nenv, ctypes.byref(a), s)
         if rc != 0:
             raise _lib.OSCError("osc_batch_rollout_env" if env else "osc_batch_rollout", rc)
+        res._keep = keep + [workspace]   # inputs and scratch stay alive until the stream is done
+        return res
+
+    def _rollout_sched(self, solver, qpos, qvel, mask, nticks, dt, T, pd, warm, history, stream,
+                       workspace, env_params, kin_params, schedule) -> "RolloutResult":
+        """rollout(..., schedule=): osc_batch_rollout_sched (include/osc_rollout_schedule.h)."""
+        if T is not None and pd is not None:
+            raise ValueError("at most one of T and pd may be given")
+        if T is None and pd is None and schedule.T is None:
+            raise ValueError("one of T, pd and schedule.T must be given")
+        d = solver.dims
+        nenv, nticks = int(qpos.shape[0]), int(nticks)
+        if nticks < 0:
+            raise ValueError("nticks < 0")
+        o = dict(device=self.device, dtype=torch.float64)
+        qpos = self._dev(qpos, (nenv, self.nq), "qpos").clone()
+        qvel = self._dev(qvel, (nenv, self.nv), "qvel").clone()
+        sc, st, per_env_seq = self._schedule(schedule, solver, nenv, nticks, pd is not None)
+        a = _lib.OscRolloutArgs()
+        a.nticks, a.dt, a.flags = nticks, float(dt), _lib.ROLLOUT_WARM if warm else 0
+        keep = [qpos, qvel, sc] + list(st.values())
+        if mask is not None:
+            mask = self._dev(mask, (nenv, d["nc"]), "mask")
+            a.contact_mask = mask.data_ptr()
+            keep.append(mask)
+        elif "mask" not in st:
+            raise ValueError("mask: None needs a schedule that carries it")
+        env = env_params is not None or kin_params is not None
+        ep, kp, blocks = self._blocks(solver, env_params, kin_params, nenv) if env else \
+            (None, None, [])
+        keep += blocks
+        if pd is not None:
+            keep += list(self._pd_args(a, pd, nenv, per_env_seq).values())
+        else:
+            a.target_mode = _lib.ROLLOUT_TARGETS_HELD
+            if T is not None:
+                T = self._dev(T, (nenv, d["ns"], 6), "T")
+                a.T = T.data_ptr()
+                keep.append(T)
+        res = RolloutResult(qpos, qvel, torch.zeros((nenv, d["nu"]), **o),
+                            torch.zeros((nenv,), device=self.device, dtype=torch.int32))
+        if history:
+            res.qpos_hist = torch.zeros((nticks + 1, nenv, self.nq), **o)
+            res.qvel_hist = torch.zeros((nticks + 1, nenv, self.nv), **o)
+            res.tau_hist = torch.zeros((nticks, nenv, d["nu"]), **o)
+            res.status_hist = torch.zeros((nticks, nenv), device=self.device, dtype=torch.int32)
+            a.qpos_hist, a.qvel_hist = res.qpos_hist.data_ptr(), res.qvel_hist.data_ptr()
+            a.tau_hist, a.status_hist = res.tau_hist.data_ptr(), res.status_hist.data_ptr()
+        if isinstance(workspace, str):
+            workspace = torch.empty((max(self.rollout_workspace_bytes(solver, nenv, nticks,
+                                                                      env=env) // 8, 2),), **o)
+        if workspace is not None:
+            a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
+        a.qpos, a.qvel = qpos.data_ptr(), qvel.data_ptr()
+        a.tau, a.bad_ticks = res.tau.data_ptr(), res.bad_ticks.data_ptr()
+        s = ctypes.c_void_p(self._stream(stream, self.device))
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().osc_batch_rollout_sched(solver._h, self._h, nenv, ctypes.byref(a),
+                                                    ctypes.byref(sc), ep, kp, s)
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_rollout_sched", rc)
         res._keep = keep + [workspace]   # inputs and scratch stay alive until the stream is done
         return res
 
@@ -553,11 +674,13 @@ class KinematicsBatch:
     ROLLOUT_GRADS = ("qpos0", "qvel0", "T") + \
         tuple("env." + k for k in ("mu", "u_lb", "u_ub", "fz_lb", "fz_ub", "w_pos", "w_rot")) + \
         tuple("kin." + k for k in KinEnvParams.FIELDS)
+    # include/osc_rollout_schedule.h's outputs (osc_rollout_schedule_grads, in its field order)
+    ROLLOUT_SCHEDULE_GRADS = ("T_seq", "pos_ref", "quat_ref", "pos_ref_seq", "quat_ref_seq", "gains")
 
     def rollout_backward(self, solver, result, mask, dt, T=None, pd=None, grad_qpos_hist=None,
                          grad_qvel_hist=None, grad_tau_hist=None, env_params=None,
                          kin_params=None, want=("qpos0", "qvel0"), stream=None,
-                         workspace="alloc") -> dict:
+                         workspace="alloc", schedule=None) -> dict:
         """osc_batch_rollout_backward: the vector-Jacobian product of rollout(..., history=True),
         one enqueue, no host sync.  `result` is that call's RolloutResult (its histories are the
         checkpoints), mask / dt / T or pd / env_params / kin_params that call's arguments.  The
@@ -566,15 +689,29 @@ class KinematicsBatch:
         (= zero); a loss on the final state is a cotangent on the last slab.  `want` names the
         gradients to compute, out of ROLLOUT_GRADS: "qpos0", "qvel0", "T" (held targets only: the
         sum over the ticks), "env.<field>" of solver.EnvParams, "kin.<field>" of KinEnvParams.
+        With schedule= (the forward's RolloutSchedule) or one of ROLLOUT_SCHEDULE_GRADS in `want`
+        the call is osc_batch_rollout_backward_sched (include/osc_rollout_schedule.h): "T_seq"
+        (nticks, nenv, ns, 6), every tick's grad_T, stored and not summed -- the gradient of
+        schedule.T, in PD mode the feed-forward's; "pos_ref" / "quat_ref", the held PD references'
+        gradients summed over the ticks; "pos_ref_seq" / "quat_ref_seq", per tick, when the
+        schedule carries the reference; "gains" (4,).  A shared reference's gradient and the
+        gains' come back summed over the envs ((3,), (4,), (nticks, 3), ...), a per-env
+        reference's per env.  dt and the mask get no gradient.
         Returns a dict name -> tensor."""
         from .solver import EnvGrads
-        if (T is None) == (pd is None):
+        want = tuple(want)
+        sched_call = schedule is not None or any(w in self.ROLLOUT_SCHEDULE_GRADS for w in want)
+        if sched_call:
+            if T is not None and pd is not None:
+                raise ValueError("at most one of T and pd may be given")
+            if T is None and pd is None and (schedule is None or schedule.T is None):
+                raise ValueError("one of T, pd and schedule.T must be given")
+        elif (T is None) == (pd is None):
             raise ValueError("exactly one of T and pd must be given")
         if result.qpos_hist is None or result.qvel_hist is None or result.status_hist is None:
             raise ValueError("rollout_backward: the forward call needs history=True")
-        want = tuple(want)
         for w in want:
-            if w not in self.ROLLOUT_GRADS:
+            if w not in self.ROLLOUT_GRADS + self.ROLLOUT_SCHEDULE_GRADS:
                 raise ValueError(f"rollout_backward: unknown gradient {w!r}")
         if not want:
             raise ValueError("rollout_backward: nothing asked for")
@@ -583,15 +720,31 @@ class KinematicsBatch:
         d = solver.dims
         nticks, nenv = int(result.status_hist.shape[0]), int(result.qpos_hist.shape[1])
         o = dict(device=self.device, dtype=torch.float64)
-        mask = self._dev(mask, (nenv, d["nc"]), "mask")
         a = _lib.OscRolloutBackwardArgs()
         a.nticks, a.dt = nticks, float(dt)
-        keep = [mask]
+        keep = []
+        sc, st, per_env_seq = (None, {}, {}) if schedule is None else \
+            self._schedule(schedule, solver, nenv, nticks, pd is not None)
+        keep += [sc] + list(st.values())
+        if mask is not None:
+            mask = self._dev(mask, (nenv, d["nc"]), "mask")
+            a.contact_mask = mask.data_ptr()
+            keep.append(mask)
+        elif "mask" not in st:
+            raise ValueError("mask: None needs a schedule that carries it")
         env = env_params is not None or kin_params is not None
         ep, kp, blocks = self._blocks(solver, env_params, kin_params, nenv) if env else \
             (None, None, [])
         keep += blocks
-        if T is not None:
+        if sched_call and pd is not None:
+            keep += list(self._pd_args(a, pd, nenv, per_env_seq).values())
+        elif sched_call:
+            a.target_mode = _lib.ROLLOUT_TARGETS_HELD
+            if T is not None:
+                T = self._dev(T, (nenv, d["ns"], 6), "T")
+                a.T = T.data_ptr()
+                keep.append(T)
+        elif T is not None:
             T = self._dev(T, (nenv, d["ns"], 6), "T")
             a.target_mode, a.T = _lib.ROLLOUT_TARGETS_HELD, T.data_ptr()
             keep.append(T)
@@ -614,7 +767,7 @@ class KinematicsBatch:
         gvh = self._grad_tensor(grad_qvel_hist, (nticks + 1, nenv, self.nv), "grad_qvel_hist")
         gth = self._grad_tensor(grad_tau_hist, (nticks, nenv, d["nu"]), "grad_tau_hist")
         ptr = lambda t: t.data_ptr() if t is not None else None
-        a.contact_mask, a.qpos_hist, a.qvel_hist = mask.data_ptr(), hq.data_ptr(), hv.data_ptr()
+        a.qpos_hist, a.qvel_hist = hq.data_ptr(), hv.data_ptr()
         a.status_hist = hs.data_ptr()
         a.grad_qpos_hist, a.grad_qvel_hist, a.grad_tau_hist = ptr(gqh), ptr(gvh), ptr(gth)
         out = RolloutGrads()
@@ -643,13 +796,48 @@ class KinematicsBatch:
         if workspace is not None:
             a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
         s = ctypes.c_void_p(self._stream(stream, self.device))
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().osc_batch_rollout_backward(solver._h, self._h, nenv, ctypes.byref(a),
-                                                       ep, kp, s)
-        if rc != 0:
-            raise _lib.OSCError("osc_batch_rollout_backward", rc)
+        if sched_call:
+            # the library's outputs are per env; a shared reference's and the gains' are summed here
+            sshape = dict(T_seq=(nticks, nenv, d["ns"], 6), pos_ref=(nenv, 3), quat_ref=(nenv, 4),
+                          pos_ref_seq=(nticks, nenv, 3), quat_ref_seq=(nticks, nenv, 4),
+                          gains=(nenv, 4))
+            raw = {w: torch.empty(sshape[w], **o) for w in want if w in sshape}
+            sg = _lib.OscRolloutScheduleGrads(**{"grad_" + w: t.data_ptr() for w, t in raw.items()})
+            with torch.cuda.device(self.device):
+                rc = _lib.lib().osc_batch_rollout_backward_sched(
+                    solver._h, self._h, nenv, ctypes.byref(a),
+                    ctypes.byref(sc) if sc is not None else None, ctypes.byref(sg), ep, kp, s)
+            if rc != 0:
+                raise _lib.OSCError("osc_batch_rollout_backward_sched", rc)
+            for w, t in raw.items():
+                if w == "gains":
+                    t = t.sum(0)
+                elif w in ("pos_ref", "quat_ref") and not getattr(a, w + "_per_env"):
+                    t = t.sum(0)
+                elif w in ("pos_ref_seq", "quat_ref_seq") and not per_env_seq[w[:-4]]:
+                    t = t.sum(1)
+                out[w] = t
+            keep += [sg] + list(raw.values())
+        else:
+            with torch.cuda.device(self.device):
+                rc = _lib.lib().osc_batch_rollout_backward(solver._h, self._h, nenv,
+                                                           ctypes.byref(a), ep, kp, s)
+            if rc != 0:
+                raise _lib.OSCError("osc_batch_rollout_backward", rc)
         out._keep = keep + [workspace, hq, hv, hs, gqh, gvh, gth]   # alive until the stream is done
         return out
+
+
+@dataclasses.dataclass
+class RolloutSchedule:
+    """Inputs of a rollout that change over its ticks (osc_rollout_schedule,
+    include/osc_rollout_schedule.h); torch tensors or numpy arrays, tick-major, each optional.
+    A base trajectory to follow is pos_ref / quat_ref; a gait is a stance / swing pattern in mask
+    with swing-foot targets in T; a target sequence to optimise is T."""
+    T: object = None          # (nticks, nenv, ns, 6): ADDED to the tick's held or PD targets
+    mask: object = None       # (nticks, nenv, nc): tick t's contact mask
+    pos_ref: object = None    # PD targets: (nticks, 3) shared or (nticks, nenv, 3) per env
+    quat_ref: object = None   # likewise with 4
 
 
 class RolloutGrads(dict):
