@@ -32,6 +32,7 @@
 #include "osc_kin_env_params.h"
 #include "osc_kin_model.hpp"
 #include "osc_kinematics.h"
+#include "osc_plant.h"
 #include "osc_producers.h"
 #include "osc_qpos.hpp"
 #include "osc_rollout.h"
@@ -43,6 +44,7 @@ using osc_kin::KinDev;
 
 // the layout bindings restate (osc_amd/_lib.py OscRolloutArgs; tests/test_rollout_ref.py)
 static_assert(sizeof(void*) != 8 || sizeof(osc_rollout_args) == 184, "osc_rollout_args layout");
+static_assert(sizeof(void*) != 8 || sizeof(osc_rollout_plant) == 32, "osc_rollout_plant layout");
 
 constexpr int kBlock = 256;
 constexpr int kEnvPerBlock = 16;
@@ -243,6 +245,23 @@ struct RolloutWorkspace {   // sections, each 256-B aligned
   }
 };
 
+// The plant's sections behind the rollout's own (include/osc_plant.h): M_p | C_p of the plant's
+// kinematics and the qacc the step integrates, each 256-B aligned.
+struct PlantWorkspace {
+  size_t mp, cp, qacc, total;
+  PlantWorkspace(const RolloutWorkspace& L, const osc_model_desc& d, int32_t nenv) {
+    const size_t n = static_cast<size_t>(nenv), dbl = sizeof(double);
+    mp = L.total;
+    cp = mp + align256(dbl * n * d.nv * d.nv);
+    qacc = cp + align256(dbl * n * d.nv);
+    total = qacc + align256(dbl * n * d.nv);
+  }
+};
+
+bool plant_active(const osc_rollout_plant* p) {
+  return p != nullptr && (p->kin_params || p->qfrc_applied || p->qfrc_applied_seq || p->qacc_hist);
+}
+
 // what both entries check of the handles: the pair describes one robot (osc_qpos_workspace_bytes
 // holds check_pair's nv / ns agreement) and the model has no wheel rows
 int check_handles(const osc_model* model, const osc_kin_model* kin, osc_model_desc* d) {
@@ -289,10 +308,14 @@ extern "C" int osc_rollout_workspace_bytes(const osc_model* model, const osc_kin
 // osc_batch_rollout (both blocks NULL: every tick through osc_batch_solve_qpos(_warm)),
 // osc_batch_rollout_env (every tick through osc_batch_solve_qpos_env, the blocks held constant)
 // and, with a schedule, osc_batch_rollout_sched (osc_rollout_schedule.h): a sequence replaces its
-// held input by tick t's slab pointer, and T_seq is added to the tick's targets in the T slab
+// held input by tick t's slab pointer, and T_seq is added to the tick's targets in the T slab.
+// With a plant that has a non-NULL field (osc_batch_rollout_plant, include/osc_plant.h) the step
+// integrates the plant's forward dynamics of the solve's u and z instead of dv; without one every
+// branch below takes its old side.
 int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
                      const osc_rollout_args* args, const osc_rollout_schedule* sched,
-                     const osc_env_params* ep, const osc_kin_env_params* kp, void* stream) {
+                     const osc_env_params* ep, const osc_kin_env_params* kp,
+                     const osc_rollout_plant* plant, void* stream) {
   // ---- every check before the first launch ----
   osc_model_desc d;
   int rc = check_handles(model, kin, &d);
@@ -302,6 +325,27 @@ int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t n
   if (kp != nullptr)
     for (const double* a : {kp->mass_scale, kp->com_offset, kp->armature_scale})
       if ((reinterpret_cast<uintptr_t>(a) & 7u) != 0) return OSC_ERR_INVALID_ARGUMENT;
+  const bool with_plant = plant_active(plant);
+  const osc_kin_env_params* pkp = with_plant ? plant->kin_params : nullptr;
+  // the plant's kinematics runs when its parameters differ from the controller's (the fused
+  // diagnostic tick leaves no M, C, J in the workspace: there it always runs)
+#ifdef OSC_FUSED_TICK
+  const bool plant_kin = with_plant;
+#else
+  const bool plant_kin = pkp != nullptr && (pkp->mass_scale || pkp->com_offset || pkp->armature_scale);
+#endif
+  if (with_plant) {
+    for (const double* a : {plant->qfrc_applied, plant->qfrc_applied_seq,
+                            static_cast<const double*>(plant->qacc_hist)})
+      if ((reinterpret_cast<uintptr_t>(a) & 7u) != 0) return OSC_ERR_INVALID_ARGUMENT;
+    if (pkp != nullptr)
+      for (const double* a : {pkp->mass_scale, pkp->com_offset, pkp->armature_scale})
+        if ((reinterpret_cast<uintptr_t>(a) & 7u) != 0) return OSC_ERR_INVALID_ARGUMENT;
+    // (the forward dynamics' own check of the model, with nothing to launch)
+    rc = osc_batch_forward_dynamics(model, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0,
+                                    nullptr, nullptr, nullptr);
+    if (rc != OSC_OK) return rc;
+  }
   if (!args || nenv < 0 || args->nticks < 0) return OSC_ERR_INVALID_ARGUMENT;
   if (!(args->dt > 0.0) || !std::isfinite(args->dt)) return OSC_ERR_INVALID_ARGUMENT;
   if (args->flags & ~OSC_ROLLOUT_WARM) return OSC_ERR_INVALID_ARGUMENT;
@@ -329,7 +373,9 @@ int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t n
   if ((reinterpret_cast<uintptr_t>(args->workspace) & 15u) != 0) return OSC_ERR_INVALID_ARGUMENT;
   const RolloutWorkspace L(model, kin, d, nenv);
   if (L.rc != OSC_OK) return L.rc;
-  if (args->workspace && args->workspace_bytes < L.total) return OSC_ERR_INVALID_ARGUMENT;
+  const PlantWorkspace LP(L, d, nenv);
+  const size_t ws_total = with_plant ? LP.total : L.total;
+  if (args->workspace && args->workspace_bytes < ws_total) return OSC_ERR_INVALID_ARGUMENT;
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int32_t nticks = args->nticks;
@@ -338,7 +384,7 @@ int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t n
   char* base = static_cast<char*>(args->workspace);
   bool owned = false;
   if (base == nullptr && nticks > 0) {
-    if (hipMallocAsync(reinterpret_cast<void**>(&base), L.total, s) != hipSuccess)
+    if (hipMallocAsync(reinterpret_cast<void**>(&base), ws_total, s) != hipSuccess)
       return OSC_ERR_DEVICE;
     owned = true;
   }
@@ -412,11 +458,38 @@ int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t n
                                        mask, tau, x, status, nullptr, base + L.qp,
                                        L.qp_bytes, stream);
     if (rc != OSC_OK) break;
+    const double* qacc = x;   // dv = x[0:nv]
+    int64_t qacc_stride = static_cast<int64_t>(nx);
+    if (with_plant) {
+      // the tick's own M, C, J (the solve reads them, const, and leaves them as the kinematics
+      // wrote them); J and b do not depend on the inertial parameters, so the plant's kinematics
+      // rewrites them with the same bits
+      const osc_kin::QposWorkspace Q(model, k, nenv);
+      const double* Mp = dptr(L.qp + Q.m);
+      const double* Cp = dptr(L.qp + Q.c);
+      if (plant_kin) {
+        rc = osc_batch_kinematics_env(kin, nenv, args->qpos, args->qvel, pkp, dptr(LP.mp),
+                                      dptr(LP.cp), dptr(L.qp + Q.j), dptr(L.qp + Q.b), nullptr,
+                                      stream);
+        if (rc != OSC_OK) break;
+        Mp = dptr(LP.mp);
+        Cp = dptr(LP.cp);
+      }
+      const double* qfrc = plant->qfrc_applied_seq ? plant->qfrc_applied_seq + n * d.nv * t
+                                                   : plant->qfrc_applied;
+      double* out = plant->qacc_hist ? plant->qacc_hist + n * d.nv * t : dptr(LP.qacc);
+      rc = osc_batch_forward_dynamics(model, nenv, Mp, Cp, dptr(L.qp + Q.j), x + d.nv,
+                                      static_cast<int64_t>(nx), x + d.nv + d.nu,
+                                      static_cast<int64_t>(nx), qfrc, out, stream);
+      if (rc != OSC_OK) break;
+      qacc = out;
+      qacc_stride = d.nv;
+    }
     StepArgs a = step_args(kin, nenv);
     a.nu = d.nu;
     a.dt = args->dt;
-    a.qacc = x;   // dv = x[0:nv]
-    a.qacc_stride = static_cast<int64_t>(nx);
+    a.qacc = qacc;
+    a.qacc_stride = qacc_stride;
     a.status = status;
     a.qpos = args->qpos;
     a.qvel = args->qvel;
@@ -439,7 +512,7 @@ int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t n
 
 extern "C" int osc_batch_rollout(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
                                  const osc_rollout_args* args, void* stream) {
-  return osc::rollout_run(model, kin, nenv, args, nullptr, nullptr, nullptr, stream);
+  return osc::rollout_run(model, kin, nenv, args, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // (the tick's workspace is osc_qpos_env_workspace_bytes, which is osc_qpos_workspace_bytes: one
@@ -452,5 +525,28 @@ extern "C" int osc_rollout_env_workspace_bytes(const osc_model* model, const osc
 extern "C" int osc_batch_rollout_env(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
                                      const osc_rollout_args* args, const osc_env_params* env_params,
                                      const osc_kin_env_params* kin_params, void* stream) {
-  return osc::rollout_run(model, kin, nenv, args, nullptr, env_params, kin_params, stream);
+  return osc::rollout_run(model, kin, nenv, args, nullptr, env_params, kin_params, nullptr, stream);
+}
+
+// ---- the rollout against a plant (include/osc_plant.h) ----
+
+extern "C" int osc_rollout_plant_workspace_bytes(const osc_model* model, const osc_kin_model* kin,
+                                                 int32_t nenv, int32_t nticks, size_t* bytes) {
+  if (!bytes || nenv < 0 || nticks < 0) return OSC_ERR_INVALID_ARGUMENT;
+  osc_model_desc d;
+  const int rc = check_handles(model, kin, &d);
+  if (rc != OSC_OK) return rc;
+  const RolloutWorkspace L(model, kin, d, nenv);
+  if (L.rc != OSC_OK) return L.rc;
+  *bytes = PlantWorkspace(L, d, nenv).total;
+  return OSC_OK;
+}
+
+extern "C" int osc_batch_rollout_plant(const osc_model* model, const osc_kin_model* kin,
+                                       int32_t nenv, const osc_rollout_args* args,
+                                       const osc_rollout_schedule* sched,
+                                       const osc_env_params* env_params,
+                                       const osc_kin_env_params* kin_params,
+                                       const osc_rollout_plant* plant, void* stream) {
+  return osc::rollout_run(model, kin, nenv, args, sched, env_params, kin_params, plant, stream);
 }

@@ -7,15 +7,17 @@
 
 #include <cstdint>
 
+#include "osc_plant.h"
 #include "osc_rollout_schedule.h"
 
 namespace osc {
 
 // osc_rollout.hip: the forward tick loop behind osc_batch_rollout(_env) (sched NULL) and
-// osc_batch_rollout_sched
+// osc_batch_rollout_sched; `plant` (include/osc_plant.h) NULL for all of those
 int rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
                 const osc_rollout_args* args, const osc_rollout_schedule* sched,
-                const osc_env_params* ep, const osc_kin_env_params* kp, void* stream);
+                const osc_env_params* ep, const osc_kin_env_params* kp,
+                const osc_rollout_plant* plant, void* stream);
 
 // osc_rollout_backward.hip: the backward tick loop behind osc_batch_rollout_backward (sched and
 // sgrads NULL: its own combine kernel, untouched) and osc_batch_rollout_backward_sched

@@ -222,7 +222,7 @@ extern "C" int osc_batch_rollout_sched(const osc_model* model, const osc_kin_mod
                                        const osc_rollout_schedule* sched,
                                        const osc_env_params* env_params,
                                        const osc_kin_env_params* kin_params, void* stream) {
-  return osc::rollout_run(model, kin, nenv, args, sched, env_params, kin_params, stream);
+  return osc::rollout_run(model, kin, nenv, args, sched, env_params, kin_params, nullptr, stream);
 }
 
 extern "C" int osc_pd_base_targets_backward_params(

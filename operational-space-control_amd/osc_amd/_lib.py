@@ -77,6 +77,10 @@ ROLLOUT_BACKWARD_SYMBOLS = ("osc_batch_integrate_backward", "osc_pd_base_targets
 # apart likewise; tests/test_rollout_schedule_ref.py pins this list to that header's declarations.
 ROLLOUT_SCHEDULE_SYMBOLS = ("osc_batch_rollout_sched", "osc_pd_base_targets_backward_params",
                             "osc_batch_rollout_backward_sched")
+# include/osc_plant.h (forward dynamics; the rollout against a mismatched plant), apart likewise;
+# tests/test_plant_ref.py pins this list to that header's declarations.
+PLANT_SYMBOLS = ("osc_batch_forward_dynamics", "osc_rollout_plant_workspace_bytes",
+                 "osc_batch_rollout_plant")
 
 OSC_KIN_MAX_BODIES = 16
 OSC_KIN_MAX_DOFS = 32
@@ -246,6 +250,12 @@ class OscRolloutScheduleGrads(ctypes.Structure):
                                                 "grad_gains")]
 
 
+class OscRolloutPlant(ctypes.Structure):
+    """osc_rollout_plant (include/osc_plant.h)."""
+    _fields_ = [("kin_params", ctypes.POINTER(OscKinEnvParams)), ("qfrc_applied", ctypes.c_void_p),
+                ("qfrc_applied_seq", ctypes.c_void_p), ("qacc_hist", ctypes.c_void_p)]
+
+
 FEED_QP, FEED_JOINT_STATES, FEED_WARM = 0, 1, 1
 
 
@@ -407,6 +417,13 @@ def lib() -> ctypes.CDLL:
                                                    ctypes.POINTER(OscRolloutBackwardArgs), scp,
                                                    sgp, ep, kep, vp]
     for name in ROLLOUT_SCHEDULE_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
+    L.osc_batch_forward_dynamics.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.c_int64, vp,
+                                             ctypes.c_int64, vp, vp, vp]
+    L.osc_rollout_plant_workspace_bytes.argtypes = [vp, vp, i32, i32, szp]
+    L.osc_batch_rollout_plant.argtypes = [vp, vp, i32, ctypes.POINTER(OscRolloutArgs), scp, ep,
+                                          kep, ctypes.POINTER(OscRolloutPlant), vp]
+    for name in PLANT_SYMBOLS:
         getattr(L, name).restype = ctypes.c_int
     L.osc_batch_solve_backward.argtypes = [vp, i32] + [vp] * 8 + [ctypes.c_size_t, vp]
     L.osc_batch_solve_backward.restype = ctypes.c_int

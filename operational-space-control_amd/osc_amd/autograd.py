@@ -371,7 +371,7 @@ class _RolloutSched(torch.autograd.Function):
 
 def rollout_differentiable(solver: OSCBatchSolver, kin: KinematicsBatch, qpos, qvel, mask,
                            nticks: int, dt: float, T=None, pd=None, warm: bool = True,
-                           env_params=None, kin_params=None, schedule=None):
+                           env_params=None, kin_params=None, schedule=None, plant=None):
     """(qpos_hist, qvel_hist, tau_hist, status_hist) of the closed-loop rollout
     (KinematicsBatch.rollout(..., history=True, schedule=...): its forward values, bitwise),
     differentiable with respect to qpos, qvel, a held T and the tensor fields of env_params (a
@@ -387,7 +387,15 @@ def rollout_differentiable(solver: OSCBatchSolver, kin: KinematicsBatch, qpos, q
     osc_batch_rollout_backward_sched, include/osc_rollout_schedule.h) that recomputes the ticks
     from the histories and fills only what autograd asks for; a loss may touch any slab of the
     three histories.  The gradient with respect to qpos is with respect to the raw nq
-    coordinates."""
+    coordinates.
+    plant (a kinematics.Plant with a field set) raises NotImplementedError: gradients through the
+    plant are out of scope (include/osc_plant.h), and the backward pass here is the matched
+    model's."""
+    if plant is not None and getattr(plant, "active", True):
+        raise NotImplementedError(
+            "rollout_differentiable: gradients through a plant are out of scope "
+            "(include/osc_plant.h, DESIGN.md §7.5); KinematicsBatch.rollout(..., plant=) runs the "
+            "forward alone")
     if env_params is not None and not isinstance(env_params, EnvParams):
         raise TypeError("rollout_differentiable: env_params must be an EnvParams")
     if kin_params is not None and not isinstance(kin_params, KinEnvParams):

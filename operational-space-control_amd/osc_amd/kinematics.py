@@ -11,6 +11,9 @@ Reference interface this mirrors (paths relative to the reference's operational-
 Beyond the reference (include/osc_rollout.h): KinematicsBatch.rollout(...) runs K closed-loop
 ticks on the device by integrating the QP's own acceleration (an idealised rollout over the
 controller's model, not a simulator), KinematicsBatch.integrate_into(...) is its step alone.
+include/osc_plant.h: KinematicsBatch.forward_dynamics(...) is qacc = M^-1 (B u + Jc' z + qfrc - C),
+and rollout(..., plant=Plant(...)) integrates that of a plant with its own mass / COM / armature
+and applied forces instead of the QP's dv (still no ground).
 The kinematic tree comes from operational-space-control_amd/config/<robot>_kinematics.json
 (illustrative trees: the reference's MJCF files are not vendored) or from any osc_kin_desc.
 Launches go through the C-ABI on the current torch stream; there is no CPU fallback.
@@ -412,10 +415,103 @@ class KinematicsBatch:
             raise _lib.OSCError("osc_batch_integrate", rc)
         return qpos, qvel
 
-    def rollout_workspace_bytes(self, solver, nenv: int, nticks: int, env: bool = False) -> int:
-        """osc_rollout_workspace_bytes, or (env) osc_rollout_env_workspace_bytes."""
+    # ---- forward dynamics and the rollout's plant (include/osc_plant.h) ----
+
+    def forward_dynamics_into(self, solver, qacc, M, C, J, u, z=None, qfrc_applied=None,
+                              stream=None):
+        """osc_batch_forward_dynamics, launch only: qacc = M^-1 (B u + Jc' z + qfrc_applied - C)
+        into qacc (nenv, nv), a contiguous float64 device tensor.  M (nenv, nv, nv), C (nenv, nv)
+        and J (nenv, 6 ns, nv; may be None when z is) are contiguous; u (nenv, nu) and z
+        (nenv, 3 nc) may be strided views with contiguous rows, such as x[:, nv:nv + nu] and
+        x[:, nv + nu:] of a solve; qfrc_applied (nenv, nv) contiguous.  z / qfrc_applied None = no
+        contact force / no applied force.  An env whose M is not positive definite, or with a
+        non-finite input, gets a NaN row."""
+        d = solver.dims
+        nenv, nv = int(qacc.shape[0]), self.nv
+        rows = dict(u=(u, d["nu"]), z=(z, 3 * d["nc"]))
+        dense = dict(qacc=(qacc, (nenv, nv)), M=(M, (nenv, nv, nv)), C=(C, (nenv, nv)),
+                     J=(J, (nenv, 6 * self.ns, nv)), qfrc_applied=(qfrc_applied, (nenv, nv)))
+        for name, (t, shape) in dense.items():
+            if t is None:
+                if name in ("qacc", "M", "C") or (name == "J" and z is not None):
+                    raise ValueError(f"{name}: required")
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or \
+                    t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"{name}: expected a contiguous float64 tensor of shape {shape} "
+                                 f"on {self.device}")
+        stride = {}
+        for name, (t, w) in rows.items():
+            if t is None:
+                if name == "u":
+                    raise ValueError("u: required")
+                stride[name] = 0
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or \
+                    t.device != self.device or tuple(t.shape) != (nenv, w) or \
+                    (w > 1 and t.stride(1) != 1):
+                raise ValueError(f"{name}: expected (nenv, {w}) float64 with contiguous rows on "
+                                 f"{self.device}")
+            stride[name] = t.stride(0) if nenv > 1 else w
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = _lib.lib().osc_batch_forward_dynamics(
+            solver._h, nenv, ptr(M), ptr(C), ptr(J), ptr(u), stride["u"], ptr(z), stride["z"],
+            ptr(qfrc_applied), ptr(qacc), ctypes.c_void_p(self._stream(stream, self.device)))
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_forward_dynamics", rc)
+        return qacc
+
+    def forward_dynamics(self, solver, qpos, qvel, tau, z=None, qfrc_applied=None,
+                         kin_params=None):
+        """qacc (nenv, nv) of joint states under torques tau (nenv, nu), contact forces z
+        (nenv, 3 nc) and generalised applied forces qfrc_applied (nenv, nv), each of the last two
+        optional: compute(kin_params=) and then forward_dynamics_into."""
+        d = solver.dims
+        nenv = int(qpos.shape[0])
+        tau = self._dev(tau, (nenv, d["nu"]), "tau")
+        z = None if z is None else self._dev(z, (nenv, 3 * d["nc"]), "z")
+        f = None if qfrc_applied is None else self._dev(qfrc_applied, (nenv, self.nv),
+                                                        "qfrc_applied")
+        k = self.compute(qpos, qvel, want_sites=False, kin_params=kin_params)
+        qacc = torch.empty((nenv, self.nv), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            return self.forward_dynamics_into(solver, qacc, k.M, k.C, k.J, tau, z, f)
+
+    def _plant_block(self, plant, res, nenv, nticks, history):
+        """(osc_rollout_plant struct, what it points to) of a rollout with plant=; with history the
+        result's qacc_hist is allocated when the plant has a field.  Shape errors raise here."""
+        if not isinstance(plant, Plant):
+            raise TypeError("plant: expected a Plant")
+        c, keep = _lib.OscRolloutPlant(), []
+        if plant.kin_params is not None:
+            kc, kk = self._kin_block(plant.kin_params, nenv)
+            keep += [kc] + kk
+            c.kin_params = ctypes.pointer(kc)
+        if plant.qfrc_applied is not None:
+            f = plant.qfrc_applied
+            f = f if isinstance(f, torch.Tensor) else np.asarray(f, dtype=np.float64)
+            if f.ndim == 3:
+                f = self._dev(f, (nticks, nenv, self.nv), "plant.qfrc_applied")
+                c.qfrc_applied_seq = f.data_ptr()
+            else:
+                f = self._dev(f, (nenv, self.nv), "plant.qfrc_applied")
+                c.qfrc_applied = f.data_ptr()
+            keep.append(f)
+        if plant.active:
+            res.plant = plant
+            if history:
+                res.qacc_hist = torch.zeros((nticks, nenv, self.nv), dtype=torch.float64,
+                                            device=self.device)
+                c.qacc_hist = res.qacc_hist.data_ptr()
+        return c, keep
+
+    def rollout_workspace_bytes(self, solver, nenv: int, nticks: int, env: bool = False,
+                                plant: bool = False) -> int:
+        """osc_rollout_workspace_bytes, (env) osc_rollout_env_workspace_bytes or (plant)
+        osc_rollout_plant_workspace_bytes."""
         nb = ctypes.c_size_t()
-        name = "osc_rollout_env_workspace_bytes" if env else "osc_rollout_workspace_bytes"
+        name = "osc_rollout_plant_workspace_bytes" if plant else \
+            "osc_rollout_env_workspace_bytes" if env else "osc_rollout_workspace_bytes"
         rc = getattr(_lib.lib(), name)(solver._h, self._h, nenv, nticks, ctypes.byref(nb))
         if rc != 0:
             raise _lib.OSCError(name, rc)
@@ -474,7 +570,7 @@ class KinematicsBatch:
     def rollout(self, solver, qpos, qvel, mask, nticks: int, dt: float, T=None, pd=None,
                 warm: bool = True, history: bool = False, stream=None,
                 workspace="alloc", env_params=None, kin_params=None,
-                schedule=None) -> "RolloutResult":
+                schedule=None, plant=None) -> "RolloutResult":
         """osc_batch_rollout: nticks ticks of kinematics -> targets -> solve -> step on the
         device, one enqueue, no host sync.  An idealised rollout over the controller's model, not
         a simulator: no ground, no contact detection; `mask` is an input, held constant unless
@@ -491,10 +587,15 @@ class KinematicsBatch:
         workspace: "alloc" = a tensor of rollout_workspace_bytes, None = the library's
         stream-ordered scratch, or a float64 device tensor.
         env_params (a solver.EnvParams) / kin_params (a KinEnvParams): osc_batch_rollout_env, both
-        blocks held constant over the rollout; an env with invalid parameters stays frozen."""
+        blocks held constant over the rollout; an env with invalid parameters stays frozen.
+        plant (a Plant): osc_batch_rollout_plant (include/osc_plant.h): the step integrates the
+        plant's forward dynamics of the tick's torques and contact forces -- its own mass / COM /
+        armature, pushed by qfrc_applied -- instead of the QP's dv; the controller keeps using
+        kin_params.  Still no ground: the contact forces are whatever the QP chose.  With
+        history=True the result carries qacc_hist.  None or Plant() is bitwise the call without."""
         if schedule is not None:
             return self._rollout_sched(solver, qpos, qvel, mask, nticks, dt, T, pd, warm, history,
-                                       stream, workspace, env_params, kin_params, schedule)
+                                       stream, workspace, env_params, kin_params, schedule, plant)
         if (T is None) == (pd is None):
             raise ValueError("exactly one of T and pd must be given")
         d = solver.dims
@@ -536,27 +637,35 @@ class KinematicsBatch:
             res.status_hist = torch.zeros((nslab, nenv), device=self.device, dtype=torch.int32)
             a.qpos_hist, a.qvel_hist = res.qpos_hist.data_ptr(), res.qvel_hist.data_ptr()
             a.tau_hist, a.status_hist = res.tau_hist.data_ptr(), res.status_hist.data_ptr()
+        pl = None
+        if plant is not None:
+            pl, pkeep = self._plant_block(plant, res, nenv, nslab, history)
+            keep += [pl] + pkeep
         if isinstance(workspace, str):
-            workspace = torch.empty((max(self.rollout_workspace_bytes(solver, nenv, nslab,
-                                                                      env=env) // 8, 2),), **o)
+            workspace = torch.empty((max(self.rollout_workspace_bytes(
+                solver, nenv, nslab, env=env, plant=pl is not None) // 8, 2),), **o)
         if workspace is not None:
             a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
         a.contact_mask, a.qpos, a.qvel = mask.data_ptr(), qpos.data_ptr(), qvel.data_ptr()
         a.tau, a.bad_ticks = res.tau.data_ptr(), res.bad_ticks.data_ptr()
         s = ctypes.c_void_p(self._stream(stream, self.device))
         with torch.cuda.device(self.device):
-            if env:
+            if pl is not None:
+                rc = _lib.lib().osc_batch_rollout_plant(solver._h, self._h, nenv, ctypes.byref(a),
+                                                        None, ep, kp, ctypes.byref(pl), s)
+            elif env:
                 rc = _lib.lib().osc_batch_rollout_env(solver._h, self._h, nenv, ctypes.byref(a),
                                                       ep, kp, s)
             else:
                 rc = _lib.lib().osc_batch_rollout(solver._h, self._h, nenv, ctypes.byref(a), s)
         if rc != 0:
-            raise _lib.OSCError("osc_batch_rollout_env" if env else "osc_batch_rollout", rc)
+            raise _lib.OSCError("osc_batch_rollout_plant" if pl is not None else
+                                "osc_batch_rollout_env" if env else "osc_batch_rollout", rc)
         res._keep = keep + [workspace]   # inputs and scratch stay alive until the stream is done
         return res
 
     def _rollout_sched(self, solver, qpos, qvel, mask, nticks, dt, T, pd, warm, history, stream,
-                       workspace, env_params, kin_params, schedule) -> "RolloutResult":
+                       workspace, env_params, kin_params, schedule, plant=None) -> "RolloutResult":
         """rollout(..., schedule=): osc_batch_rollout_sched (include/osc_rollout_schedule.h)."""
         if T is not None and pd is not None:
             raise ValueError("at most one of T and pd may be given")
@@ -600,19 +709,29 @@ class KinematicsBatch:
             res.status_hist = torch.zeros((nticks, nenv), device=self.device, dtype=torch.int32)
             a.qpos_hist, a.qvel_hist = res.qpos_hist.data_ptr(), res.qvel_hist.data_ptr()
             a.tau_hist, a.status_hist = res.tau_hist.data_ptr(), res.status_hist.data_ptr()
+        pl = None
+        if plant is not None:
+            pl, pkeep = self._plant_block(plant, res, nenv, nticks, history)
+            keep += [pl] + pkeep
         if isinstance(workspace, str):
-            workspace = torch.empty((max(self.rollout_workspace_bytes(solver, nenv, nticks,
-                                                                      env=env) // 8, 2),), **o)
+            workspace = torch.empty((max(self.rollout_workspace_bytes(
+                solver, nenv, nticks, env=env, plant=pl is not None) // 8, 2),), **o)
         if workspace is not None:
             a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
         a.qpos, a.qvel = qpos.data_ptr(), qvel.data_ptr()
         a.tau, a.bad_ticks = res.tau.data_ptr(), res.bad_ticks.data_ptr()
         s = ctypes.c_void_p(self._stream(stream, self.device))
         with torch.cuda.device(self.device):
-            rc = _lib.lib().osc_batch_rollout_sched(solver._h, self._h, nenv, ctypes.byref(a),
-                                                    ctypes.byref(sc), ep, kp, s)
+            if pl is not None:
+                rc = _lib.lib().osc_batch_rollout_plant(solver._h, self._h, nenv, ctypes.byref(a),
+                                                        ctypes.byref(sc), ep, kp,
+                                                        ctypes.byref(pl), s)
+            else:
+                rc = _lib.lib().osc_batch_rollout_sched(solver._h, self._h, nenv, ctypes.byref(a),
+                                                        ctypes.byref(sc), ep, kp, s)
         if rc != 0:
-            raise _lib.OSCError("osc_batch_rollout_sched", rc)
+            raise _lib.OSCError("osc_batch_rollout_plant" if pl is not None else
+                                "osc_batch_rollout_sched", rc)
         res._keep = keep + [workspace]   # inputs and scratch stay alive until the stream is done
         return res
 
@@ -699,6 +818,11 @@ class KinematicsBatch:
         reference's per env.  dt and the mask get no gradient.
         Returns a dict name -> tensor."""
         from .solver import EnvGrads
+        if getattr(result, "plant", None) is not None:
+            raise NotImplementedError(
+                "rollout_backward: the result came from a rollout against a plant; gradients "
+                "through the plant are out of scope (include/osc_plant.h, DESIGN.md §7.5) and "
+                "the matched model's would be wrong for it")
         want = tuple(want)
         sched_call = schedule is not None or any(w in self.ROLLOUT_SCHEDULE_GRADS for w in want)
         if sched_call:
@@ -840,6 +964,21 @@ class RolloutSchedule:
     quat_ref: object = None   # likewise with 4
 
 
+@dataclasses.dataclass
+class Plant:
+    """The plant of a rollout when it is not the controller's model (osc_rollout_plant,
+    include/osc_plant.h).  kin_params: the PLANT's KinEnvParams (None = the controller's own);
+    qfrc_applied: MuJoCo's generalised applied force, (nenv, nv) held over the rollout or
+    (nticks, nenv, nv) per tick -- on a free root, entries 0..2 are a world-frame force at the base
+    origin; a wrench on another body is the caller's J' f.  Plant() with neither is no plant."""
+    kin_params: object = None
+    qfrc_applied: object = None
+
+    @property
+    def active(self) -> bool:
+        return self.kin_params is not None or self.qfrc_applied is not None
+
+
 class RolloutGrads(dict):
     """rollout_backward's result: gradient name -> tensor."""
     _keep: list | None = None
@@ -855,6 +994,8 @@ class RolloutResult:
     qvel_hist: torch.Tensor | None = None     # (nticks + 1, nenv, nv)
     tau_hist: torch.Tensor | None = None      # (nticks, nenv, nu)
     status_hist: torch.Tensor | None = None   # (nticks, nenv) int32
+    qacc_hist: torch.Tensor | None = None     # (nticks, nenv, nv): a plant rollout's accelerations
+    plant: object = None                      # the Plant the rollout ran against (None: matched)
     _keep: list | None = None
 
 
