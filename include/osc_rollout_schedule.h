@@ -16,9 +16,9 @@
  * Launches.  A sequence that replaces a held input is a pointer offset per tick: T_seq alone in
  * held mode (args->T NULL), mask_seq and the reference sequences launch nothing.  T_seq ADDED to
  * a held T or to the PD producer's targets is one flat elementwise kernel per tick, a separate
- * IEEE addition of the producer's already rounded value.  The backward replaces the combine
- * kernel of osc_rollout_backward.h by one that, in the same launch, also stores the tick's grad_T
- * and forms the reference and gain adjoints; the recompute's addition is its only extra launch.
+ * IEEE addition of the producer's already rounded value.  The backward's combine
+ * kernel (osc_rollout_backward.h) also stores the tick's grad_T and forms the reference and gain
+ * adjoints, in the same launch; the recompute's addition is its only extra launch.
  */
 #ifndef OSC_ROLLOUT_SCHEDULE_H_
 #define OSC_ROLLOUT_SCHEDULE_H_

@@ -17,11 +17,13 @@
 // coordinate: the freeze decision (any non-finite qacc entry) and a quaternion's update, which
 // needs its four components and three rates; the four lanes of a quaternion each compute the
 // rotation and store their own component.  Joint types and addresses come from the kinematics
-// model's device tables (jtype, qadr, dadr), turned into a per-coordinate map once per block.
+// model's device tables (jtype, qadr, dadr), turned into the per-block JointMaps
+// (osc_rollout_internal.hpp) the step adjoint uses too.
 //
-// The PD targets themselves are produced by the existing osc_pd_base_targets kernel from the
-// packed base state the step writes (one more small launch per tick in PD mode): its result is
-// then bitwise the producer's by construction, and osc_producers.hip stays untouched.
+// The PD targets themselves are produced by the osc_pd_base_targets kernel from the packed base
+// state the step writes (one more small launch per tick in PD mode): its result is then bitwise
+// the producer's by construction.  A tick's targets, mask and references come from
+// osc::tick_inputs (osc_rollout_schedule.hip), which the backward's recompute calls as well.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -36,20 +38,16 @@
 #include "osc_producers.h"
 #include "osc_qpos.hpp"
 #include "osc_rollout.h"
-#include "osc_rollout_sched.hpp"
+#include "osc_rollout_internal.hpp"
 
 namespace {
 
+using namespace osc;   // osc_rollout_internal.hpp's geometry, helpers and joint maps
 using osc_kin::KinDev;
 
 // the layout bindings restate (osc_amd/_lib.py OscRolloutArgs; tests/test_rollout_ref.py)
 static_assert(sizeof(void*) != 8 || sizeof(osc_rollout_args) == 184, "osc_rollout_args layout");
 static_assert(sizeof(void*) != 8 || sizeof(osc_rollout_plant) == 32, "osc_rollout_plant layout");
-
-constexpr int kBlock = 256;
-constexpr int kEnvPerBlock = 16;
-// every joint has at most one more coordinate than dofs, and there is at most one joint per body
-constexpr int kMaxNq = OSC_KIN_MAX_DOFS + OSC_KIN_MAX_BODIES;
 
 struct StepArgs {
   const KinDev* K;
@@ -100,8 +98,7 @@ __device__ __forceinline__ void quat_step(const double* q, const double* w, doub
 __global__ __launch_bounds__(kBlock) void osc_rollout_step_kernel(StepArgs a) {
   __shared__ double sq[kEnvPerBlock * kMaxNq];              // the block's qpos rows (old)
   __shared__ double sv[kEnvPerBlock * OSC_KIN_MAX_DOFS];    // qacc, then the new qvel rows
-  __shared__ int16_t cdof[kMaxNq];    // coordinate -> its dof (quaternion: its first rate)
-  __shared__ int8_t ccomp[kMaxNq];    // coordinate -> quaternion component 0..3, -1 = q += qd dt
+  __shared__ JointMaps maps;          // (the coordinate -> dof half is what the step reads)
   __shared__ int32_t sfrozen[kEnvPerBlock];
   const int tid = threadIdx.x;
   const int nq = a.nq, nv = a.nv, nu = a.nu;
@@ -111,27 +108,7 @@ __global__ __launch_bounds__(kBlock) void osc_rollout_step_kernel(StepArgs a) {
   const bool step = a.qacc != nullptr;
   const double dt = a.dt;
 
-  if (tid < a.nbody) {
-    const int jt = a.K->jtype[tid], qa = a.K->qadr[tid], da = a.K->dadr[tid];
-    if (jt == OSC_KIN_JOINT_FREE) {
-      for (int i = 0; i < 3; ++i) {
-        cdof[qa + i] = static_cast<int16_t>(da + i);
-        ccomp[qa + i] = -1;
-      }
-      for (int i = 0; i < 4; ++i) {
-        cdof[qa + 3 + i] = static_cast<int16_t>(da + 3);
-        ccomp[qa + 3 + i] = static_cast<int8_t>(i);
-      }
-    } else if (jt == OSC_KIN_JOINT_BALL) {
-      for (int i = 0; i < 4; ++i) {
-        cdof[qa + i] = static_cast<int16_t>(da);
-        ccomp[qa + i] = static_cast<int8_t>(i);
-      }
-    } else if (jt == OSC_KIN_JOINT_HINGE || jt == OSC_KIN_JOINT_SLIDE) {
-      cdof[qa] = static_cast<int16_t>(da);
-      ccomp[qa] = -1;
-    }   // welded: no coordinate
-  }
+  build_maps(a.K, a.nbody, tid, maps);
   if (tid < kEnvPerBlock)
     sfrozen[tid] = (step && a.status && tid < ne)
                        ? (a.status[e0 + tid] == OSC_SOLVE_NUMERICAL ? 1 : 0) : 0;
@@ -182,7 +159,7 @@ __global__ __launch_bounds__(kBlock) void osc_rollout_step_kernel(StepArgs a) {
     double qn = sq[idx];
     if (step && !sfrozen[el]) {
       const double* v = sv + el * nv;
-      const int comp = ccomp[i], dof = cdof[i];
+      const int comp = maps.ccomp[i], dof = maps.cdof[i];
       if (comp < 0) {
         qn = fma(v[dof], dt, qn);
       } else {
@@ -201,12 +178,9 @@ __global__ __launch_bounds__(kBlock) void osc_rollout_step_kernel(StepArgs a) {
 }
 
 int launch_step(const StepArgs& a, hipStream_t s) {
-  static_assert(kMaxNq <= 127, "ccomp / cdof index types");
   if (a.nq > kMaxNq || a.nv > OSC_KIN_MAX_DOFS || a.nbody > OSC_KIN_MAX_BODIES)
     return OSC_ERR_INVALID_ARGUMENT;   // the kernel's LDS rows (build_tables cannot produce these)
-  const unsigned nblk = static_cast<unsigned>((static_cast<long long>(a.nenv) + kEnvPerBlock - 1) /
-                                              kEnvPerBlock);
-  hipLaunchKernelGGL(osc_rollout_step_kernel, dim3(nblk), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(osc_rollout_step_kernel, dim3(env_blocks(a.nenv)), dim3(kBlock), 0, s, a);
   return hipGetLastError() == hipSuccess ? OSC_OK : OSC_ERR_DEVICE;
 }
 
@@ -219,8 +193,6 @@ StepArgs step_args(const osc_kin_model* kin, int32_t nenv) {
   a.nbody = kin->host.nbody;
   return a;
 }
-
-size_t align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
 
 struct RolloutWorkspace {   // sections, each 256-B aligned
   size_t T, x, tau, status, bpos, bquat, blin, bang, warm, warm_bytes, qp, qp_bytes, total;
@@ -262,18 +234,6 @@ bool plant_active(const osc_rollout_plant* p) {
   return p != nullptr && (p->kin_params || p->qfrc_applied || p->qfrc_applied_seq || p->qacc_hist);
 }
 
-// what both entries check of the handles: the pair describes one robot (osc_qpos_workspace_bytes
-// holds check_pair's nv / ns agreement) and the model has no wheel rows
-int check_handles(const osc_model* model, const osc_kin_model* kin, osc_model_desc* d) {
-  if (!model || !kin) return OSC_ERR_INVALID_ARGUMENT;
-  size_t probe = 0;
-  const int rc = osc_qpos_workspace_bytes(model, kin, 0, &probe);
-  if (rc != OSC_OK) return rc;
-  if (osc_model_get_desc(model, d) != OSC_OK) return OSC_ERR_INVALID_ARGUMENT;
-  if (d->wheel_rows) return OSC_ERR_INVALID_ARGUMENT;
-  return OSC_OK;
-}
-
 }  // namespace
 
 extern "C" int osc_batch_integrate(const osc_kin_model* kin, int32_t nenv, double dt,
@@ -310,8 +270,7 @@ extern "C" int osc_rollout_workspace_bytes(const osc_model* model, const osc_kin
 // and, with a schedule, osc_batch_rollout_sched (osc_rollout_schedule.h): a sequence replaces its
 // held input by tick t's slab pointer, and T_seq is added to the tick's targets in the T slab.
 // With a plant that has a non-NULL field (osc_batch_rollout_plant, include/osc_plant.h) the step
-// integrates the plant's forward dynamics of the solve's u and z instead of dv; without one every
-// branch below takes its old side.
+// integrates the plant's forward dynamics of the solve's u and z instead of dv.
 int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
                      const osc_rollout_args* args, const osc_rollout_schedule* sched,
                      const osc_env_params* ep, const osc_kin_env_params* kp,
@@ -324,7 +283,7 @@ int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t n
   if (ep != nullptr && !osc::env_tick_ok(model, ep, nullptr)) return OSC_ERR_INVALID_ARGUMENT;
   if (kp != nullptr)
     for (const double* a : {kp->mass_scale, kp->com_offset, kp->armature_scale})
-      if ((reinterpret_cast<uintptr_t>(a) & 7u) != 0) return OSC_ERR_INVALID_ARGUMENT;
+      if (!aligned8(a)) return OSC_ERR_INVALID_ARGUMENT;
   const bool with_plant = plant_active(plant);
   const osc_kin_env_params* pkp = with_plant ? plant->kin_params : nullptr;
   // the plant's kinematics runs when its parameters differ from the controller's (the fused
@@ -337,10 +296,10 @@ int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t n
   if (with_plant) {
     for (const double* a : {plant->qfrc_applied, plant->qfrc_applied_seq,
                             static_cast<const double*>(plant->qacc_hist)})
-      if ((reinterpret_cast<uintptr_t>(a) & 7u) != 0) return OSC_ERR_INVALID_ARGUMENT;
+      if (!aligned8(a)) return OSC_ERR_INVALID_ARGUMENT;
     if (pkp != nullptr)
       for (const double* a : {pkp->mass_scale, pkp->com_offset, pkp->armature_scale})
-        if ((reinterpret_cast<uintptr_t>(a) & 7u) != 0) return OSC_ERR_INVALID_ARGUMENT;
+        if (!aligned8(a)) return OSC_ERR_INVALID_ARGUMENT;
     // (the forward dynamics' own check of the model, with nothing to launch)
     rc = osc_batch_forward_dynamics(model, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0,
                                     nullptr, nullptr, nullptr);
@@ -358,18 +317,12 @@ int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t n
   const osc_rollout_schedule sc = sched ? *sched : osc_rollout_schedule{};
   if (!pd && (sc.pos_ref_seq || sc.quat_ref_seq)) return OSC_ERR_INVALID_ARGUMENT;
   for (const double* a : {sc.T_seq, sc.mask_seq, sc.pos_ref_seq, sc.quat_ref_seq})
-    if ((reinterpret_cast<uintptr_t>(a) & 7u) != 0) return OSC_ERR_INVALID_ARGUMENT;
+    if (!aligned8(a)) return OSC_ERR_INVALID_ARGUMENT;
   if (nenv == 0) return OSC_OK;
-  // (with a schedule and no tick every sequence is empty, so nothing can stand in for a held
-  // input, and nothing reads one)
-  const bool inputs_read = !sched || args->nticks > 0;
   if (!args->qpos || !args->qvel) return OSC_ERR_INVALID_ARGUMENT;
-  if (inputs_read && d.nc > 0 && !args->contact_mask && !sc.mask_seq)
-    return OSC_ERR_INVALID_ARGUMENT;
-  if (inputs_read &&
-      (pd ? ((!args->pos_ref && !sc.pos_ref_seq) || (!args->quat_ref && !sc.quat_ref_seq))
-          : (!args->T && !sc.T_seq)))
-    return OSC_ERR_INVALID_ARGUMENT;
+  const HeldInputs held{pd, args->T, args->contact_mask, args->pos_ref, args->pos_ref_per_env,
+                        args->quat_ref, args->quat_ref_per_env, args->gains};
+  if (!tick_inputs_present(held, sched, args->nticks, d.nc)) return OSC_ERR_INVALID_ARGUMENT;
   if ((reinterpret_cast<uintptr_t>(args->workspace) & 15u) != 0) return OSC_ERR_INVALID_ARGUMENT;
   const RolloutWorkspace L(model, kin, d, nenv);
   if (L.rc != OSC_OK) return L.rc;
@@ -420,30 +373,12 @@ int osc::rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t n
 
   // ---- ticks ----
   for (int32_t t = 0; t < nticks && rc == OSC_OK; ++t) {
-    const double* T = args->T;
-    const double* mask = sc.mask_seq ? sc.mask_seq + n * d.nc * t : args->contact_mask;
-    if (pd) {
-      const double* pos_ref =
-          sc.pos_ref_seq ? sc.pos_ref_seq + (args->pos_ref_per_env ? n * 3 : 3) * t : args->pos_ref;
-      const double* quat_ref = sc.quat_ref_seq
-                                   ? sc.quat_ref_seq + (args->quat_ref_per_env ? n * 4 : 4) * t
-                                   : args->quat_ref;
-      rc = osc_pd_base_targets(nenv, d.ns, dptr(L.bpos), dptr(L.bquat), dptr(L.blin), dptr(L.bang),
-                               pos_ref, args->pos_ref_per_env, quat_ref, args->quat_ref_per_env,
-                               args->gains, Tbuf, stream);
-      T = Tbuf;
-      if (rc != OSC_OK) break;
-    }
-    if (sc.T_seq) {   // T_t = T + T_seq[t]; nothing to add to: the slab itself
-      const double* add = sc.T_seq + n * d.ns * 6 * t;
-      if (T) {
-        rc = osc::launch_sched_add(T, add, Tbuf, static_cast<long long>(n) * d.ns * 6, s);
-        T = Tbuf;
-        if (rc != OSC_OK) break;
-      } else {
-        T = add;
-      }
-    }
+    TickInputs in;
+    rc = tick_inputs(held, sc, t, nenv, d, dptr(L.bpos), dptr(L.bquat), dptr(L.blin), dptr(L.bang),
+                     Tbuf, stream, &in);
+    if (rc != OSC_OK) break;
+    const double* T = in.T;
+    const double* mask = in.mask;
     int32_t* status = args->status_hist ? args->status_hist + n * t : status_ws;
     if (env)
       rc = osc_batch_solve_qpos_env(model, kin, nenv, args->qpos, args->qvel, T, mask,

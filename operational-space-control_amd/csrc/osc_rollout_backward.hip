@@ -2,12 +2,14 @@
 // in include/osc_rollout_backward.h): for t = K-1 .. 0 the tick is recomputed from history slab t
 // and differentiated by the library's single-tick backward passes; this unit adds the adjoint of
 // the semi-implicit Euler step, the adjoint of the PD base-target producer and the tick-to-tick
-// reduction, and nothing else -- no existing kernel or unit changes.
+// reduction.  One tick loop serves the plain and the scheduled entries
+// (include/osc_rollout_schedule.h); the tick's inputs are resolved by osc::tick_inputs, as in the
+// forward's loop.
 //
-// Two kernels of this unit run per tick, both with osc_rollout.hip's step mapping (a 256-thread
-// block owns 16 consecutive envs and walks them with a flat env x coordinate index; what is per
-// env rather than per coordinate goes through LDS; joint types and addresses come from the
-// kinematics model's device tables, turned into per-coordinate and per-dof maps once per block):
+// Two kernels of this unit run per tick, both with the step kernel's mapping (a 256-thread block
+// owns 16 consecutive envs and walks them with a flat env x coordinate index; what is per env
+// rather than per coordinate goes through LDS; joint types and addresses come from the kinematics
+// model's device tables, turned into the per-block JointMaps of osc_rollout_internal.hpp):
 //   step adjoint  g_q, g_v of slab t + 1  ->  grad_x = (dt v', grad_tau, 0) for the solve's backward
 //                 and, in place, the step's direct part of slab t's adjoints.  A quaternion's four
 //                 lanes each need all four cotangent components, the old quaternion and the three
@@ -16,7 +18,11 @@
 //                 adjoint and keeps its own output -- one owning lane per output, no atomics.
 //   combine       g[t] = step-direct + kinematics + PD + cotangent of slab t, in that order; the
 //                 tick-ordered sums of the target and parameter gradients; in PD mode the packed
-//                 base state of slab t - 1 for the next tick's producer call.
+//                 base state of slab t - 1 for the next tick's producer call.  The same launch
+//                 writes what a scheduled call asks for, each behind a NULL check: tick t's
+//                 grad_T into its slab, and the reference and gain adjoints from slab t's base
+//                 state -- eleven outputs per env (3 + 4 + 4), one owning lane each, 176 lanes
+//                 of the block.  No atomics, no LDS.
 // Both move about a KB per env and are launch-latency bound, as the forward's step kernel is.
 #include <hip/hip_runtime.h>
 
@@ -30,21 +36,18 @@
 #include "osc_producers.h"
 #include "osc_qpos.hpp"
 #include "osc_rollout_backward.h"
-#include "osc_rollout_sched.hpp"
+#include "osc_rollout_internal.hpp"
 
 namespace {
 
+using namespace osc;   // osc_rollout_internal.hpp's geometry, helpers, joint maps and adjoints
 using osc_kin::KinDev;
 
 // the layout bindings restate (osc_amd/_lib.py OscRolloutBackwardArgs)
 static_assert(sizeof(void*) != 8 || sizeof(osc_rollout_backward_args) == 208,
               "osc_rollout_backward_args layout");
 
-constexpr int kBlock = 256;
-constexpr int kEnvPerBlock = 16;
-constexpr int kMaxNq = OSC_KIN_MAX_DOFS + OSC_KIN_MAX_BODIES;   // as osc_rollout.hip
 constexpr int kMaxAcc = 11;   // grad_T, seven osc_env_grads fields, three osc_kin_env_grads fields
-static_assert(osc::kSchedMaxAcc == kMaxAcc, "the scheduled combine holds the same sums");
 
 // a (x) b, quaternions (w, x, y, z)
 __device__ __forceinline__ void quat_mul(const double* a, const double* b, double* o) {
@@ -98,58 +101,6 @@ __device__ __forceinline__ void quat_step_adjoint(const double* q, const double*
   gw[0] = dt * (A * gd[1] + k * r[0]);
   gw[1] = dt * (A * gd[2] + k * r[1]);
   gw[2] = dt * (A * gd[3] + k * r[2]);
-}
-
-// The adjoint of osc_pd_base_targets' rotation error vec(q_ref (x) conj(q)) with respect to the
-// raw quaternion q, component `comp` of it: g = kp_ang x the cotangent of T[0][3:6].
-__device__ __forceinline__ double pd_quat_adjoint(const double* qr, const double* g, int comp) {
-  const double aw = qr[0], ax = qr[1], ay = qr[2], az = qr[3];
-  return comp == 0   ? ax * g[0] + ay * g[1] + az * g[2]
-         : comp == 1 ? -(aw * g[0] + az * g[1] - ay * g[2])
-         : comp == 2 ? -(aw * g[1] - az * g[0] + ax * g[2])
-                     : -(aw * g[2] + ay * g[0] - ax * g[1]);
-}
-
-// per-coordinate and per-dof joint maps of the block, from the kinematics model's tables
-struct JointMaps {
-  int16_t cdof[kMaxNq];             // coordinate -> its dof (quaternion: its first rate)
-  int8_t ccomp[kMaxNq];             // coordinate -> quaternion component 0..3, -1 = q += qd dt
-  int16_t dcoord[OSC_KIN_MAX_DOFS]; // dof -> its coordinate (a quaternion's rate: its w component)
-  int8_t dcomp[OSC_KIN_MAX_DOFS];   // dof -> rate component 0..2 of a quaternion, -1 = scalar
-};
-
-__device__ __forceinline__ void build_maps(const KinDev* K, int nbody, int tid, JointMaps& m) {
-  if (tid < nbody) {
-    const int jt = K->jtype[tid], qa = K->qadr[tid], da = K->dadr[tid];
-    if (jt == OSC_KIN_JOINT_FREE) {
-      for (int i = 0; i < 3; ++i) {
-        m.cdof[qa + i] = static_cast<int16_t>(da + i);
-        m.ccomp[qa + i] = -1;
-        m.dcoord[da + i] = static_cast<int16_t>(qa + i);
-        m.dcomp[da + i] = -1;
-        m.dcoord[da + 3 + i] = static_cast<int16_t>(qa + 3);
-        m.dcomp[da + 3 + i] = static_cast<int8_t>(i);
-      }
-      for (int i = 0; i < 4; ++i) {
-        m.cdof[qa + 3 + i] = static_cast<int16_t>(da + 3);
-        m.ccomp[qa + 3 + i] = static_cast<int8_t>(i);
-      }
-    } else if (jt == OSC_KIN_JOINT_BALL) {
-      for (int i = 0; i < 4; ++i) {
-        m.cdof[qa + i] = static_cast<int16_t>(da);
-        m.ccomp[qa + i] = static_cast<int8_t>(i);
-      }
-      for (int i = 0; i < 3; ++i) {
-        m.dcoord[da + i] = static_cast<int16_t>(qa);
-        m.dcomp[da + i] = static_cast<int8_t>(i);
-      }
-    } else if (jt == OSC_KIN_JOINT_HINGE || jt == OSC_KIN_JOINT_SLIDE) {
-      m.cdof[qa] = static_cast<int16_t>(da);
-      m.ccomp[qa] = -1;
-      m.dcoord[da] = static_cast<int16_t>(qa);
-      m.dcomp[da] = -1;
-    }   // welded: no coordinate
-  }
 }
 
 struct StepAdjArgs {
@@ -244,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void osc_rollout_step_adjoint_kernel(StepAd
     }
 }
 
-struct AccPair {
+struct CombineAcc {
   double* acc;         // [nenv][cnt] the running sum
   const double* src;   // [nenv][cnt] this tick's term
   int32_t cnt;
@@ -258,7 +209,10 @@ struct CombineArgs {
   const double* kv;
   const double* hq;           // slab t of grad_qpos_hist / grad_qvel_hist, nullable
   const double* hv;
-  const double* gT;           // PD mode: this tick's grad_T [nenv][ns][6]; NULL = held
+  const double* gT;           // this tick's grad_T [nenv][ns][6]; NULL = not formed
+  int32_t pd;                 // PD mode: gT reaches the base coordinates
+  const double* pos_ref;      // PD mode: tick t's references
+  int32_t pos_ref_stride;
   const double* quat_ref;
   int32_t quat_ref_stride;
   double kp_lin, kd_lin, kp_ang, kd_ang;
@@ -269,7 +223,16 @@ struct CombineArgs {
   double* blin;
   double* bang;
   int32_t nacc;
-  AccPair acc[kMaxAcc];
+  CombineAcc acc[kMaxAcc];
+  // ---- the schedule's outputs (osc_rollout_schedule_grads), all NULL for the plain entry ----
+  double* gT_slab;            // grad_T_seq[t], nullable
+  const double* qpos;         // slab t of qpos_hist / qvel_hist: the producer's base state
+  const double* qvel;
+  double* gpos_ref;           // [nenv][3]; nullable
+  double* gquat_ref;          // [nenv][4]; nullable
+  double* ggains;             // [nenv][4]; nullable: always added to
+  int32_t pos_ref_add;        // 1: gpos_ref is a running sum (a held reference); 0: this tick's slab
+  int32_t quat_ref_add;       // likewise gquat_ref
 };
 
 __global__ __launch_bounds__(kBlock) void osc_rollout_combine_kernel(CombineArgs a) {
@@ -279,12 +242,14 @@ __global__ __launch_bounds__(kBlock) void osc_rollout_combine_kernel(CombineArgs
   const long long left = a.nenv - e0;
   const int ne = left < kEnvPerBlock ? static_cast<int>(left) : kEnvPerBlock;
   const long long trow = 6LL * a.ns;
+  const bool pd = a.pd != 0;
 
+  // ---- slab t's state adjoints, the tick-ordered sums, the next tick's packed base state ----
   for (int idx = tid; idx < ne * nq; idx += kBlock) {
     const int el = idx / nq, i = idx - el * nq;
     const long long g = e0 * nq + idx, e = e0 + el;
     double v = a.gq[g] + a.kq[g];
-    if (a.gT && i < 7) {   // free root: qpos[0:3] position, qpos[3:7] quaternion
+    if (pd && i < 7) {   // free root: qpos[0:3] position, qpos[3:7] quaternion
       const double* t = a.gT + e * trow;
       if (i < 3) {
         v += -a.kp_lin * t[i];
@@ -305,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void osc_rollout_combine_kernel(CombineArgs
     const int el = idx / nv, d = idx - el * nv;
     const long long g = e0 * nv + idx, e = e0 + el;
     double v = a.gv[g] + a.kv[g];
-    if (a.gT && d < 6) v += -(d < 3 ? a.kd_lin : a.kd_ang) * a.gT[e * trow + d];
+    if (pd && d < 6) v += -(d < 3 ? a.kd_lin : a.kd_ang) * a.gT[e * trow + d];
     if (a.hv) v += a.hv[g];
     a.gv[g] = v;
     if (a.pack_qvel && d < 6) {
@@ -318,6 +283,33 @@ __global__ __launch_bounds__(kBlock) void osc_rollout_combine_kernel(CombineArgs
     const long long cnt = a.acc[k].cnt, base = e0 * cnt;
     for (long long idx = tid; idx < ne * cnt; idx += kBlock)
       a.acc[k].acc[base + idx] += a.acc[k].src[base + idx];
+  }
+
+  // ---- the schedule's: tick t's grad_T, stored; the reference and gain adjoints ----
+  // (they read gT, the history slab and the references only: nothing written above)
+  if (a.gT_slab)
+    for (long long idx = tid; idx < ne * trow; idx += kBlock)
+      a.gT_slab[e0 * trow + idx] = a.gT[e0 * trow + idx];
+  if ((a.gpos_ref || a.gquat_ref || a.ggains) && tid < ne * kParamOut) {
+    const int el = tid / kParamOut, j = tid - el * kParamOut;
+    const long long e = e0 + el;
+    double* out = j < 3 ? a.gpos_ref : j < 7 ? a.gquat_ref : a.ggains;
+    if (out) {
+      const double* q = a.qpos + e * nq;
+      const double* v = a.qvel + e * nv;
+      const double r = pd_param_adjoint(j, a.gT + e * trow, q, q + 3, v, v + 3,
+                                        a.pos_ref + e * a.pos_ref_stride,
+                                        a.quat_ref + e * a.quat_ref_stride, a.kp_lin, a.kp_ang);
+      if (j < 3) {
+        if (a.pos_ref_add) out[e * 3 + j] += r;
+        else out[e * 3 + j] = r;
+      } else if (j < 7) {
+        if (a.quat_ref_add) out[e * 4 + (j - 3)] += r;
+        else out[e * 4 + (j - 3)] = r;
+      } else {
+        out[e * 4 + (j - 7)] += r;
+      }
+    }
   }
 }
 
@@ -359,20 +351,7 @@ __global__ __launch_bounds__(kBlock) void osc_pd_base_targets_backward_kernel(
   }
 }
 
-unsigned env_blocks(int32_t nenv) {
-  return static_cast<unsigned>((static_cast<long long>(nenv) + kEnvPerBlock - 1) / kEnvPerBlock);
-}
-
-unsigned grid_for(long long n) {
-  long long b = (n + kBlock - 1) / kBlock;
-  if (b > 65535LL * 8) b = 65535LL * 8;
-  return static_cast<unsigned>(b < 1 ? 1 : b);
-}
-
-bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 int launch_step_adjoint(const StepAdjArgs& a, hipStream_t s) {
-  static_assert(kMaxNq <= 127, "JointMaps index types");
   if (a.nq > kMaxNq || a.nv > OSC_KIN_MAX_DOFS || a.nbody > OSC_KIN_MAX_BODIES)
     return OSC_ERR_INVALID_ARGUMENT;   // the kernel's LDS rows (build_tables cannot produce these)
   hipLaunchKernelGGL(osc_rollout_step_adjoint_kernel, dim3(env_blocks(a.nenv)), dim3(kBlock), 0, s,
@@ -380,9 +359,8 @@ int launch_step_adjoint(const StepAdjArgs& a, hipStream_t s) {
   return hipGetLastError() == hipSuccess ? OSC_OK : OSC_ERR_DEVICE;
 }
 
-size_t align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
-
 constexpr int kEnvFields = 7, kKinFields = 3;
+static_assert(1 + kEnvFields + kKinFields <= kMaxAcc, "CombineArgs holds every running sum");
 
 struct BackwardWorkspace {   // sections, each 256-B aligned (byte offsets)
   size_t M, C, J, b, T, x, y, tau, status, gx, gM, gC, gJ, gb, gT, gq, gv, kq, kv, bpos, bquat,
@@ -445,17 +423,6 @@ struct BackwardWorkspace {   // sections, each 256-B aligned (byte offsets)
     total = qp + align256(qp_bytes);
   }
 };
-
-// as osc_rollout.hip: the pair describes one robot and the model has no wheel rows
-int check_handles(const osc_model* model, const osc_kin_model* kin, osc_model_desc* d) {
-  if (!model || !kin) return OSC_ERR_INVALID_ARGUMENT;
-  size_t probe = 0;
-  const int rc = osc_qpos_workspace_bytes(model, kin, 0, &probe);
-  if (rc != OSC_OK) return rc;
-  if (osc_model_get_desc(model, d) != OSC_OK) return OSC_ERR_INVALID_ARGUMENT;
-  if (d->wheel_rows) return OSC_ERR_INVALID_ARGUMENT;
-  return OSC_OK;
-}
 
 }  // namespace
 
@@ -545,8 +512,8 @@ extern "C" int osc_batch_rollout_backward(const osc_model* model, const osc_kin_
 }
 
 // osc_batch_rollout_backward (sched and sgrads NULL) and osc_batch_rollout_backward_sched
-// (osc_rollout_schedule.h): the recompute of tick t on the schedule's slabs, and the scheduled
-// combine kernel in place of this unit's whenever a schedule or one of its gradients is given
+// (osc_rollout_schedule.h): the recompute of tick t on the schedule's slabs, and the schedule's
+// gradients out of the same combine launch
 int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
                               const osc_rollout_backward_args* args,
                               const osc_rollout_schedule* sched,
@@ -598,7 +565,6 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
   const osc_rollout_schedule_grads sg = sgrads ? *sgrads : osc_rollout_schedule_grads{};
   const bool any_sg = sg.grad_T_seq || sg.grad_pos_ref || sg.grad_quat_ref ||
                       sg.grad_pos_ref_seq || sg.grad_quat_ref_seq || sg.grad_gains;
-  const bool scheduled = any_sg || sc.T_seq || sc.mask_seq || sc.pos_ref_seq || sc.quat_ref_seq;
   if (!pd && (sc.pos_ref_seq || sc.quat_ref_seq || sg.grad_pos_ref || sg.grad_quat_ref ||
               sg.grad_pos_ref_seq || sg.grad_quat_ref_seq || sg.grad_gains))
     return OSC_ERR_INVALID_ARGUMENT;
@@ -626,14 +592,9 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
   if ((reinterpret_cast<uintptr_t>(args->status_hist) & 3u) != 0) return OSC_ERR_INVALID_ARGUMENT;
   if (nenv == 0) return OSC_OK;
   const int32_t nticks = args->nticks;
-  // (as the forward: with a schedule and no tick nothing reads a held input or a sequence)
-  const bool inputs_read = !sched || nticks > 0;
-  if (inputs_read && d.nc > 0 && !args->contact_mask && !sc.mask_seq)
-    return OSC_ERR_INVALID_ARGUMENT;
-  if (inputs_read &&
-      (pd ? ((!args->pos_ref && !sc.pos_ref_seq) || (!args->quat_ref && !sc.quat_ref_seq))
-          : (!args->T && !sc.T_seq)))
-    return OSC_ERR_INVALID_ARGUMENT;
+  const HeldInputs held{pd, args->T, args->contact_mask, args->pos_ref, args->pos_ref_per_env,
+                        args->quat_ref, args->quat_ref_per_env, args->gains};
+  if (!tick_inputs_present(held, sched, nticks, d.nc)) return OSC_ERR_INVALID_ARGUMENT;
   if (nticks > 0 && (!args->qpos_hist || !args->qvel_hist || !args->status_hist))
     return OSC_ERR_INVALID_ARGUMENT;
   if ((reinterpret_cast<uintptr_t>(args->workspace) & 15u) != 0) return OSC_ERR_INVALID_ARGUMENT;
@@ -715,30 +676,12 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
     rc = kp ? osc_batch_kinematics_env(kin, nenv, qpos, qvel, kp, M, C, J, b, nullptr, stream)
             : osc_batch_kinematics(kin, nenv, qpos, qvel, M, C, J, b, nullptr, stream);
     if (rc != OSC_OK) break;
-    const double* T = args->T;
-    const double* mask = sc.mask_seq ? sc.mask_seq + n * d.nc * t : args->contact_mask;
-    const double* pos_ref =
-        sc.pos_ref_seq ? sc.pos_ref_seq + (args->pos_ref_per_env ? n * 3 : 3) * t : args->pos_ref;
-    const double* quat_ref =
-        sc.quat_ref_seq ? sc.quat_ref_seq + (args->quat_ref_per_env ? n * 4 : 4) * t
-                        : args->quat_ref;
-    if (pd) {
-      rc = osc_pd_base_targets(nenv, d.ns, dptr(L.bpos), dptr(L.bquat), dptr(L.blin), dptr(L.bang),
-                               pos_ref, args->pos_ref_per_env, quat_ref, args->quat_ref_per_env,
-                               args->gains, dptr(L.T), stream);
-      T = dptr(L.T);
-      if (rc != OSC_OK) break;
-    }
-    if (sc.T_seq) {   // as the forward: T_t = T + T_seq[t], or the slab itself
-      const double* add = sc.T_seq + n * s6 * t;
-      if (T) {
-        rc = osc::launch_sched_add(T, add, dptr(L.T), static_cast<long long>(n * s6), s);
-        T = dptr(L.T);
-        if (rc != OSC_OK) break;
-      } else {
-        T = add;
-      }
-    }
+    TickInputs in;
+    rc = tick_inputs(held, sc, t, nenv, d, dptr(L.bpos), dptr(L.bquat), dptr(L.blin), dptr(L.bang),
+                     dptr(L.T), stream, &in);
+    if (rc != OSC_OK) break;
+    const double* T = in.T;
+    const double* mask = in.mask;
     osc_solve_extras ex{};
     ex.y = dptr(L.y);
     rc = ep ? osc_batch_solve_env(model, nenv, M, C, J, b, T, mask, ep, &ex,
@@ -787,59 +730,7 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
                                        any_kg ? &kg_tick : nullptr, stream);
     if (rc != OSC_OK) break;
     // ---- combine: slab t's adjoints, the tick-ordered sums, the next tick's base state ----
-    if (scheduled) {   // the same, and the schedule's outputs, in one launch
-      osc::SchedCombineArgs c{};
-      c.nenv = nenv;
-      c.nq = k.nq;
-      c.nv = k.nv;
-      c.ns = d.ns;
-      c.gq = gq;
-      c.gv = gv;
-      c.kq = dptr(L.kq);
-      c.kv = dptr(L.kv);
-      c.hq = args->grad_qpos_hist ? args->grad_qpos_hist + n * nq * t : nullptr;
-      c.hv = args->grad_qvel_hist ? args->grad_qvel_hist + n * nv * t : nullptr;
-      c.gT = gT;
-      if (pd) {
-        c.pd = 1;
-        c.pos_ref = pos_ref;
-        c.pos_ref_stride = args->pos_ref_per_env ? 3 : 0;
-        c.quat_ref = quat_ref;
-        c.quat_ref_stride = args->quat_ref_per_env ? 4 : 0;
-        c.kp_lin = args->gains[0];
-        c.kd_lin = args->gains[1];
-        c.kp_ang = args->gains[2];
-        c.kd_ang = args->gains[3];
-        if (t > 0) {
-          c.pack_qpos = args->qpos_hist + n * nq * (t - 1);
-          c.pack_qvel = args->qvel_hist + n * nv * (t - 1);
-          c.bpos = dptr(L.bpos);
-          c.bquat = dptr(L.bquat);
-          c.blin = dptr(L.blin);
-          c.bang = dptr(L.bang);
-        }
-        c.qpos = qpos;
-        c.qvel = qvel;
-        c.gpos_ref = sg.grad_pos_ref_seq ? sg.grad_pos_ref_seq + n * 3 * t : sg.grad_pos_ref;
-        c.pos_ref_add = sg.grad_pos_ref_seq ? 0 : 1;
-        c.gquat_ref = sg.grad_quat_ref_seq ? sg.grad_quat_ref_seq + n * 4 * t : sg.grad_quat_ref;
-        c.quat_ref_add = sg.grad_quat_ref_seq ? 0 : 1;
-        c.ggains = sg.grad_gains;
-      }
-      c.gT_slab = sg.grad_T_seq ? sg.grad_T_seq + n * s6 * t : nullptr;
-      if (args->grad_T)
-        c.acc[c.nacc++] = osc::SchedAcc{args->grad_T, gT, static_cast<int32_t>(s6)};
-      for (int i = 0; i < kEnvFields; ++i)
-        if (eg_out[i])
-          c.acc[c.nacc++] =
-              osc::SchedAcc{eg_out[i], dptr(L.eg[i]), static_cast<int32_t>(L.eg_cnt[i])};
-      for (int i = 0; i < kKinFields; ++i)
-        if (kg_out[i])
-          c.acc[c.nacc++] =
-              osc::SchedAcc{kg_out[i], dptr(L.kg[i]), static_cast<int32_t>(L.kg_cnt[i])};
-      rc = osc::launch_sched_combine(c, s);
-      continue;
-    }
+    // (the plain entry has no schedule gradient: sg's pointers are NULL, and so are c's)
     CombineArgs c{};
     c.nenv = nenv;
     c.nq = k.nq;
@@ -851,9 +742,12 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
     c.kv = dptr(L.kv);
     c.hq = args->grad_qpos_hist ? args->grad_qpos_hist + n * nq * t : nullptr;
     c.hv = args->grad_qvel_hist ? args->grad_qvel_hist + n * nv * t : nullptr;
+    c.gT = gT;
     if (pd) {
-      c.gT = gT;
-      c.quat_ref = args->quat_ref;
+      c.pd = 1;
+      c.pos_ref = in.pos_ref;
+      c.pos_ref_stride = args->pos_ref_per_env ? 3 : 0;
+      c.quat_ref = in.quat_ref;
       c.quat_ref_stride = args->quat_ref_per_env ? 4 : 0;
       c.kp_lin = args->gains[0];
       c.kd_lin = args->gains[1];
@@ -867,14 +761,24 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
         c.blin = dptr(L.blin);
         c.bang = dptr(L.bang);
       }
+      c.qpos = qpos;
+      c.qvel = qvel;
+      c.gpos_ref = sg.grad_pos_ref_seq ? sg.grad_pos_ref_seq + n * 3 * t : sg.grad_pos_ref;
+      c.pos_ref_add = sg.grad_pos_ref_seq ? 0 : 1;
+      c.gquat_ref = sg.grad_quat_ref_seq ? sg.grad_quat_ref_seq + n * 4 * t : sg.grad_quat_ref;
+      c.quat_ref_add = sg.grad_quat_ref_seq ? 0 : 1;
+      c.ggains = sg.grad_gains;
     }
-    if (args->grad_T) c.acc[c.nacc++] = AccPair{args->grad_T, gT, static_cast<int32_t>(s6)};
+    c.gT_slab = sg.grad_T_seq ? sg.grad_T_seq + n * s6 * t : nullptr;
+    if (args->grad_T) c.acc[c.nacc++] = CombineAcc{args->grad_T, gT, static_cast<int32_t>(s6)};
     for (int i = 0; i < kEnvFields; ++i)
       if (eg_out[i])
-        c.acc[c.nacc++] = AccPair{eg_out[i], dptr(L.eg[i]), static_cast<int32_t>(L.eg_cnt[i])};
+        c.acc[c.nacc++] =
+            CombineAcc{eg_out[i], dptr(L.eg[i]), static_cast<int32_t>(L.eg_cnt[i])};
     for (int i = 0; i < kKinFields; ++i)
       if (kg_out[i])
-        c.acc[c.nacc++] = AccPair{kg_out[i], dptr(L.kg[i]), static_cast<int32_t>(L.kg_cnt[i])};
+        c.acc[c.nacc++] =
+            CombineAcc{kg_out[i], dptr(L.kg[i]), static_cast<int32_t>(L.kg_cnt[i])};
     hipLaunchKernelGGL(osc_rollout_combine_kernel, dim3(env_blocks(nenv)), dim3(kBlock), 0, s, c);
     rc = ok(hipGetLastError());
   }

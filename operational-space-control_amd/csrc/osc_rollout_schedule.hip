@@ -1,31 +1,28 @@
 // osc_rollout_schedule.hip -- the scheduled rollout (C-ABI in include/osc_rollout_schedule.h):
 // per-tick targets, masks and PD references in the forward, and in the backward the per-tick
 // grad_T and the gradients with respect to the PD references and gains.  The tick loops are
-// osc_rollout.hip's and osc_rollout_backward.hip's own (osc_rollout_sched.hpp); this unit holds
-// the three kernels they need and the entry points.  No existing kernel changes.
+// osc_rollout.hip's and osc_rollout_backward.hip's; this unit holds what a schedule adds to them:
+// the resolution of one tick's inputs, which both loops call (the backward recomputes the
+// forward's tick, so the two must agree bit for bit), the addition kernel it launches, the
+// stand-alone PD parameter adjoint and the scheduled entry points.
 //
 // The per-tick glue is launch-latency bound (osc_rollout.hip's header), so a scheduled tick adds
-// at most ONE small launch to a plain one, and none where a pointer offset does the job:
-//   forward   a sequence that replaces a held input (T_seq with args->T NULL, mask_seq, the
-//             reference sequences) is tick t's slab pointer.  T_seq added to a held T or to the
-//             producer's targets is sched_add_kernel: flat over nenv x ns x 6, consecutive lanes on
-//             consecutive doubles.  The producer's value is already rounded and in memory when
-//             the addition reads it, and the kernel holds no multiplication, so nothing can
-//             contract across the two: the sum is bitwise osc_pd_base_targets followed by one
-//             IEEE addition.
-//   backward  sched_combine_kernel is osc_rollout_backward.hip's combine kernel -- its statements
-//             verbatim, so the state adjoints and the tick-ordered sums round as they do there --
-//             and in the same launch stores the tick's grad_T into its slab and forms the
-//             reference and gain adjoints from slab t's base state, read from the histories.  Eleven
-//             outputs per env (3 + 4 + 4), one owning lane each: 176 lanes of the 256-thread block
-//             that owns 16 consecutive envs, as every kernel of the rollout.  No atomics, no LDS.
+// at most ONE small launch to a plain one, and none where a pointer offset does the job: a
+// sequence that replaces a held input (T_seq with args->T NULL, mask_seq, the reference sequences)
+// is tick t's slab pointer.  T_seq added to a held T or to the producer's targets is
+// sched_add_kernel: flat over nenv x ns x 6, consecutive lanes on consecutive doubles.  The
+// producer's value is already rounded and in memory when the addition reads it, and the kernel
+// holds no multiplication, so nothing can contract across the two: the sum is bitwise
+// osc_pd_base_targets followed by one IEEE addition.  In the backward the schedule's outputs are
+// written by the one combine kernel (osc_rollout_backward.hip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
 #include "osc_batch.h"
-#include "osc_rollout_sched.hpp"
+#include "osc_producers.h"
+#include "osc_rollout_internal.hpp"
 #include "osc_rollout_schedule.h"
 
 namespace {
@@ -36,55 +33,13 @@ static_assert(sizeof(void*) != 8 || sizeof(osc_rollout_schedule) == 32,
 static_assert(sizeof(void*) != 8 || sizeof(osc_rollout_schedule_grads) == 48,
               "osc_rollout_schedule_grads layout");
 
-constexpr int kBlock = 256;
-constexpr int kEnvPerBlock = 16;
-constexpr int kParamOut = 11;   // grad_pos_ref 3, grad_quat_ref 4, grad_gains 4
-static_assert(kEnvPerBlock * kParamOut <= kBlock, "one owning lane per parameter output");
+using namespace osc;   // osc_rollout_internal.hpp's geometry, helpers and adjoints
 
 __global__ __launch_bounds__(kBlock) void osc_rollout_sched_add_kernel(
     long long count, const double* base, const double* add, double* out) {
   for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < count;
        i += static_cast<long long>(gridDim.x) * kBlock)
     out[i] = __dadd_rn(base[i], add[i]);   // out may alias base: each lane reads before it writes
-}
-
-// as osc_rollout_backward.hip's: component `comp` of the adjoint of vec(q_ref (x) conj(q)) with
-// respect to the raw quaternion q; g = kp_ang x the cotangent of T[0][3:6]
-__device__ __forceinline__ double pd_quat_adjoint(const double* qr, const double* g, int comp) {
-  const double aw = qr[0], ax = qr[1], ay = qr[2], az = qr[3];
-  return comp == 0   ? ax * g[0] + ay * g[1] + az * g[2]
-         : comp == 1 ? -(aw * g[0] + az * g[1] - ay * g[2])
-         : comp == 2 ? -(aw * g[1] - az * g[0] + ax * g[2])
-                     : -(aw * g[2] + ay * g[0] - ax * g[1]);
-}
-
-// Output j of one env's adjoint of osc_pd_base_targets with respect to its parameters: 0..2
-// grad_pos_ref, 3..6 grad_quat_ref, 7..10 grad_gains.  t = the cotangent of row 0 of the targets,
-//   T[0][0:3] = kp_l (p_ref - p) + kd_l (0 - v),   T[0][3:6] = kp_a vec(q_ref (x) conj(q)) + kd_a (0 - w)
-// (osc_producers.hip's expressions for the error terms, so the gains' adjoints weigh bitwise the
-// errors the forward scaled).
-__device__ __forceinline__ double pd_param_adjoint(int j, const double* t, const double* p,
-                                                   const double* q, const double* v,
-                                                   const double* w, const double* pr,
-                                                   const double* qr, double kp_lin,
-                                                   double kp_ang) {
-  if (j < 3) return kp_lin * t[j];
-  const double bw = q[0], bx = -q[1], by = -q[2], bz = -q[3];
-  if (j < 7) {
-    const double g0 = kp_ang * t[3], g1 = kp_ang * t[4], g2 = kp_ang * t[5];
-    return j == 3   ? bx * g0 + by * g1 + bz * g2
-           : j == 4 ? bw * g0 - bz * g1 + by * g2
-           : j == 5 ? bz * g0 + bw * g1 - bx * g2
-                    : -by * g0 + bx * g1 + bw * g2;
-  }
-  if (j == 7) return (pr[0] - p[0]) * t[0] + (pr[1] - p[1]) * t[1] + (pr[2] - p[2]) * t[2];
-  if (j == 8) return (0.0 - v[0]) * t[0] + (0.0 - v[1]) * t[1] + (0.0 - v[2]) * t[2];
-  if (j == 10) return (0.0 - w[0]) * t[3] + (0.0 - w[1]) * t[4] + (0.0 - w[2]) * t[5];
-  const double aw = qr[0], ax = qr[1], ay = qr[2], az = qr[3];
-  const double rx = aw * bx + ax * bw + ay * bz - az * by;
-  const double ry = aw * by - ax * bz + ay * bw + az * bx;
-  const double rz = aw * bz + ax * by - ay * bx + az * bw;
-  return rx * t[3] + ry * t[4] + rz * t[5];
 }
 
 __global__ __launch_bounds__(kBlock) void osc_pd_base_targets_backward_params_kernel(
@@ -109,97 +64,6 @@ __global__ __launch_bounds__(kBlock) void osc_pd_base_targets_backward_params_ke
   }
 }
 
-__global__ __launch_bounds__(kBlock) void osc_rollout_sched_combine_kernel(
-    osc::SchedCombineArgs a) {
-  const int tid = threadIdx.x;
-  const int nq = a.nq, nv = a.nv;
-  const long long e0 = static_cast<long long>(blockIdx.x) * kEnvPerBlock;
-  const long long left = a.nenv - e0;
-  const int ne = left < kEnvPerBlock ? static_cast<int>(left) : kEnvPerBlock;
-  const long long trow = 6LL * a.ns;
-  const bool pd = a.pd != 0;
-
-  // ---- osc_rollout_combine_kernel's statements ----
-  for (int idx = tid; idx < ne * nq; idx += kBlock) {
-    const int el = idx / nq, i = idx - el * nq;
-    const long long g = e0 * nq + idx, e = e0 + el;
-    double v = a.gq[g] + a.kq[g];
-    if (pd && i < 7) {   // free root: qpos[0:3] position, qpos[3:7] quaternion
-      const double* t = a.gT + e * trow;
-      if (i < 3) {
-        v += -a.kp_lin * t[i];
-      } else {
-        const double ga[3] = {a.kp_ang * t[3], a.kp_ang * t[4], a.kp_ang * t[5]};
-        v += pd_quat_adjoint(a.quat_ref + e * a.quat_ref_stride, ga, i - 3);
-      }
-    }
-    if (a.hq) v += a.hq[g];
-    a.gq[g] = v;
-    if (a.pack_qpos && i < 7) {
-      const double s = a.pack_qpos[g];
-      if (i < 3) a.bpos[e * 3 + i] = s;
-      else a.bquat[e * 4 + (i - 3)] = s;
-    }
-  }
-  for (int idx = tid; idx < ne * nv; idx += kBlock) {
-    const int el = idx / nv, d = idx - el * nv;
-    const long long g = e0 * nv + idx, e = e0 + el;
-    double v = a.gv[g] + a.kv[g];
-    if (pd && d < 6) v += -(d < 3 ? a.kd_lin : a.kd_ang) * a.gT[e * trow + d];
-    if (a.hv) v += a.hv[g];
-    a.gv[g] = v;
-    if (a.pack_qvel && d < 6) {
-      const double s = a.pack_qvel[g];
-      if (d < 3) a.blin[e * 3 + d] = s;
-      else a.bang[e * 3 + (d - 3)] = s;
-    }
-  }
-  for (int k = 0; k < a.nacc; ++k) {
-    const long long cnt = a.acc[k].cnt, base = e0 * cnt;
-    for (long long idx = tid; idx < ne * cnt; idx += kBlock)
-      a.acc[k].acc[base + idx] += a.acc[k].src[base + idx];
-  }
-
-  // ---- the schedule's: tick t's grad_T, stored; the reference and gain adjoints ----
-  // (they read gT, the history slab and the references only: nothing written above)
-  if (a.gT_slab)
-    for (long long idx = tid; idx < ne * trow; idx += kBlock)
-      a.gT_slab[e0 * trow + idx] = a.gT[e0 * trow + idx];
-  if ((a.gpos_ref || a.gquat_ref || a.ggains) && tid < ne * kParamOut) {
-    const int el = tid / kParamOut, j = tid - el * kParamOut;
-    const long long e = e0 + el;
-    double* out = j < 3 ? a.gpos_ref : j < 7 ? a.gquat_ref : a.ggains;
-    if (out) {
-      const double* q = a.qpos + e * nq;
-      const double* v = a.qvel + e * nv;
-      const double r = pd_param_adjoint(j, a.gT + e * trow, q, q + 3, v, v + 3,
-                                        a.pos_ref + e * a.pos_ref_stride,
-                                        a.quat_ref + e * a.quat_ref_stride, a.kp_lin, a.kp_ang);
-      if (j < 3) {
-        if (a.pos_ref_add) out[e * 3 + j] += r;
-        else out[e * 3 + j] = r;
-      } else if (j < 7) {
-        if (a.quat_ref_add) out[e * 4 + (j - 3)] += r;
-        else out[e * 4 + (j - 3)] = r;
-      } else {
-        out[e * 4 + (j - 7)] += r;
-      }
-    }
-  }
-}
-
-unsigned grid_for(long long n) {
-  long long b = (n + kBlock - 1) / kBlock;
-  if (b > 65535LL * 8) b = 65535LL * 8;
-  return static_cast<unsigned>(b < 1 ? 1 : b);
-}
-
-bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
-}  // namespace
-
-namespace osc {
-
 int launch_sched_add(const double* base, const double* add, double* out, long long count,
                      hipStream_t s) {
   if (count <= 0) return OSC_OK;
@@ -208,14 +72,48 @@ int launch_sched_add(const double* base, const double* add, double* out, long lo
   return hipGetLastError() == hipSuccess ? OSC_OK : OSC_ERR_DEVICE;
 }
 
-int launch_sched_combine(const SchedCombineArgs& a, hipStream_t s) {
-  const unsigned nblk = static_cast<unsigned>((static_cast<long long>(a.nenv) + kEnvPerBlock - 1) /
-                                              kEnvPerBlock);
-  hipLaunchKernelGGL(osc_rollout_sched_combine_kernel, dim3(nblk), dim3(kBlock), 0, s, a);
-  return hipGetLastError() == hipSuccess ? OSC_OK : OSC_ERR_DEVICE;
+}  // namespace
+
+bool osc::tick_inputs_present(const HeldInputs& in, const osc_rollout_schedule* sched,
+                              int32_t nticks, int32_t nc) {
+  if (sched && nticks <= 0) return true;
+  const osc_rollout_schedule sc = sched ? *sched : osc_rollout_schedule{};
+  if (nc > 0 && !in.contact_mask && !sc.mask_seq) return false;
+  return in.pd ? (in.pos_ref || sc.pos_ref_seq) && (in.quat_ref || sc.quat_ref_seq)
+               : in.T || sc.T_seq;
 }
 
-}  // namespace osc
+int osc::tick_inputs(const HeldInputs& in, const osc_rollout_schedule& sc, int32_t t,
+                     int32_t nenv, const osc_model_desc& d, const double* bpos,
+                     const double* bquat, const double* blin, const double* bang, double* Tbuf,
+                     void* stream, TickInputs* out) {
+  const size_t n = static_cast<size_t>(nenv), s6 = 6 * static_cast<size_t>(d.ns);
+  out->T = in.T;
+  out->mask = sc.mask_seq ? sc.mask_seq + n * d.nc * t : in.contact_mask;
+  out->pos_ref =
+      sc.pos_ref_seq ? sc.pos_ref_seq + (in.pos_ref_per_env ? n * 3 : 3) * t : in.pos_ref;
+  out->quat_ref =
+      sc.quat_ref_seq ? sc.quat_ref_seq + (in.quat_ref_per_env ? n * 4 : 4) * t : in.quat_ref;
+  if (in.pd) {
+    const int rc = osc_pd_base_targets(nenv, d.ns, bpos, bquat, blin, bang, out->pos_ref,
+                                       in.pos_ref_per_env, out->quat_ref, in.quat_ref_per_env,
+                                       in.gains, Tbuf, stream);
+    if (rc != OSC_OK) return rc;
+    out->T = Tbuf;
+  }
+  if (sc.T_seq) {   // T_t = T + T_seq[t]; nothing to add to: the slab itself
+    const double* add = sc.T_seq + n * s6 * t;
+    if (!out->T) {
+      out->T = add;
+    } else {
+      const int rc = launch_sched_add(out->T, add, Tbuf, static_cast<long long>(n * s6),
+                                      static_cast<hipStream_t>(stream));
+      if (rc != OSC_OK) return rc;
+      out->T = Tbuf;
+    }
+  }
+  return OSC_OK;
+}
 
 extern "C" int osc_batch_rollout_sched(const osc_model* model, const osc_kin_model* kin,
                                        int32_t nenv, const osc_rollout_args* args,

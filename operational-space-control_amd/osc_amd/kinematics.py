@@ -567,6 +567,18 @@ class KinematicsBatch:
         a.gains[:] = [float(g) for g in gains]
         return refs
 
+    def _target_args(self, a, T, pd, nenv, d, per_env_seq):
+        """Fill a's target fields: PD targets from pd (_pd_args), else held targets T (None: the
+        schedule's T alone).  Returns the tensors a points to."""
+        if pd is not None:
+            return [r for r in self._pd_args(a, pd, nenv, per_env_seq).values() if r is not None]
+        a.target_mode = _lib.ROLLOUT_TARGETS_HELD
+        if T is None:
+            return []
+        T = self._dev(T, (nenv, d["ns"], 6), "T")
+        a.T = T.data_ptr()
+        return [T]
+
     def rollout(self, solver, qpos, qvel, mask, nticks: int, dt: float, T=None, pd=None,
                 warm: bool = True, history: bool = False, stream=None,
                 workspace="alloc", env_params=None, kin_params=None,
@@ -593,43 +605,36 @@ class KinematicsBatch:
         armature, pushed by qfrc_applied -- instead of the QP's dv; the controller keeps using
         kin_params.  Still no ground: the contact forces are whatever the QP chose.  With
         history=True the result carries qacc_hist.  None or Plant() is bitwise the call without."""
-        if schedule is not None:
-            return self._rollout_sched(solver, qpos, qvel, mask, nticks, dt, T, pd, warm, history,
-                                       stream, workspace, env_params, kin_params, schedule, plant)
-        if (T is None) == (pd is None):
-            raise ValueError("exactly one of T and pd must be given")
+        if T is not None and pd is not None:
+            raise ValueError("at most one of T and pd may be given")
+        if T is None and pd is None and (schedule is None or schedule.T is None):
+            raise ValueError("one of T, pd and schedule.T must be given")
         d = solver.dims
         nenv, nticks = int(qpos.shape[0]), int(nticks)
+        if schedule is not None and nticks < 0:
+            raise ValueError("nticks < 0")
+        nslab = max(nticks, 0)      # (a negative nticks without a schedule: the library's refusal)
         o = dict(device=self.device, dtype=torch.float64)
         qpos = self._dev(qpos, (nenv, self.nq), "qpos").clone()
         qvel = self._dev(qvel, (nenv, self.nv), "qvel").clone()
-        mask = self._dev(mask, (nenv, d["nc"]), "mask")
+        sc, st, per_env_seq = (None, {}, {}) if schedule is None else \
+            self._schedule(schedule, solver, nenv, nticks, pd is not None)
         a = _lib.OscRolloutArgs()
         a.nticks, a.dt, a.flags = nticks, float(dt), _lib.ROLLOUT_WARM if warm else 0
-        keep = [qpos, qvel, mask]
+        keep = [qpos, qvel, sc] + list(st.values())
+        if mask is not None:
+            mask = self._dev(mask, (nenv, d["nc"]), "mask")
+            a.contact_mask = mask.data_ptr()
+            keep.append(mask)
+        elif "mask" not in st:
+            raise ValueError("mask: None needs a schedule that carries it")
         env = env_params is not None or kin_params is not None
         ep, kp, blocks = self._blocks(solver, env_params, kin_params, nenv) if env else \
             (None, None, [])
         keep += blocks
-        if T is not None:
-            T = self._dev(T, (nenv, d["ns"], 6), "T")
-            a.target_mode, a.T = _lib.ROLLOUT_TARGETS_HELD, T.data_ptr()
-            keep.append(T)
-        else:
-            pos_ref, quat_ref, gains = pd
-            pos_ref, quat_ref = (r if isinstance(r, torch.Tensor) else
-                                 np.asarray(r, dtype=np.float64) for r in (pos_ref, quat_ref))
-            per_env = [int(r.ndim == 2) for r in (pos_ref, quat_ref)]
-            pos_ref = self._dev(pos_ref, (nenv, 3) if per_env[0] else (3,), "pos_ref")
-            quat_ref = self._dev(quat_ref, (nenv, 4) if per_env[1] else (4,), "quat_ref")
-            a.target_mode = _lib.ROLLOUT_TARGETS_PD_BASE
-            a.pos_ref, a.pos_ref_per_env = pos_ref.data_ptr(), per_env[0]
-            a.quat_ref, a.quat_ref_per_env = quat_ref.data_ptr(), per_env[1]
-            a.gains[:] = [float(g) for g in gains]
-            keep += [pos_ref, quat_ref]
+        keep += self._target_args(a, T, pd, nenv, d, per_env_seq)
         res = RolloutResult(qpos, qvel, torch.zeros((nenv, d["nu"]), **o),
                             torch.zeros((nenv,), device=self.device, dtype=torch.int32))
-        nslab = max(nticks, 0)
         if history:
             res.qpos_hist = torch.zeros((nslab + 1, nenv, self.nq), **o)
             res.qvel_hist = torch.zeros((nslab + 1, nenv, self.nv), **o)
@@ -646,92 +651,23 @@ class KinematicsBatch:
                 solver, nenv, nslab, env=env, plant=pl is not None) // 8, 2),), **o)
         if workspace is not None:
             a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
-        a.contact_mask, a.qpos, a.qvel = mask.data_ptr(), qpos.data_ptr(), qvel.data_ptr()
-        a.tau, a.bad_ticks = res.tau.data_ptr(), res.bad_ticks.data_ptr()
-        s = ctypes.c_void_p(self._stream(stream, self.device))
-        with torch.cuda.device(self.device):
-            if pl is not None:
-                rc = _lib.lib().osc_batch_rollout_plant(solver._h, self._h, nenv, ctypes.byref(a),
-                                                        None, ep, kp, ctypes.byref(pl), s)
-            elif env:
-                rc = _lib.lib().osc_batch_rollout_env(solver._h, self._h, nenv, ctypes.byref(a),
-                                                      ep, kp, s)
-            else:
-                rc = _lib.lib().osc_batch_rollout(solver._h, self._h, nenv, ctypes.byref(a), s)
-        if rc != 0:
-            raise _lib.OSCError("osc_batch_rollout_plant" if pl is not None else
-                                "osc_batch_rollout_env" if env else "osc_batch_rollout", rc)
-        res._keep = keep + [workspace]   # inputs and scratch stay alive until the stream is done
-        return res
-
-    def _rollout_sched(self, solver, qpos, qvel, mask, nticks, dt, T, pd, warm, history, stream,
-                       workspace, env_params, kin_params, schedule, plant=None) -> "RolloutResult":
-        """rollout(..., schedule=): osc_batch_rollout_sched (include/osc_rollout_schedule.h)."""
-        if T is not None and pd is not None:
-            raise ValueError("at most one of T and pd may be given")
-        if T is None and pd is None and schedule.T is None:
-            raise ValueError("one of T, pd and schedule.T must be given")
-        d = solver.dims
-        nenv, nticks = int(qpos.shape[0]), int(nticks)
-        if nticks < 0:
-            raise ValueError("nticks < 0")
-        o = dict(device=self.device, dtype=torch.float64)
-        qpos = self._dev(qpos, (nenv, self.nq), "qpos").clone()
-        qvel = self._dev(qvel, (nenv, self.nv), "qvel").clone()
-        sc, st, per_env_seq = self._schedule(schedule, solver, nenv, nticks, pd is not None)
-        a = _lib.OscRolloutArgs()
-        a.nticks, a.dt, a.flags = nticks, float(dt), _lib.ROLLOUT_WARM if warm else 0
-        keep = [qpos, qvel, sc] + list(st.values())
-        if mask is not None:
-            mask = self._dev(mask, (nenv, d["nc"]), "mask")
-            a.contact_mask = mask.data_ptr()
-            keep.append(mask)
-        elif "mask" not in st:
-            raise ValueError("mask: None needs a schedule that carries it")
-        env = env_params is not None or kin_params is not None
-        ep, kp, blocks = self._blocks(solver, env_params, kin_params, nenv) if env else \
-            (None, None, [])
-        keep += blocks
-        if pd is not None:
-            keep += list(self._pd_args(a, pd, nenv, per_env_seq).values())
-        else:
-            a.target_mode = _lib.ROLLOUT_TARGETS_HELD
-            if T is not None:
-                T = self._dev(T, (nenv, d["ns"], 6), "T")
-                a.T = T.data_ptr()
-                keep.append(T)
-        res = RolloutResult(qpos, qvel, torch.zeros((nenv, d["nu"]), **o),
-                            torch.zeros((nenv,), device=self.device, dtype=torch.int32))
-        if history:
-            res.qpos_hist = torch.zeros((nticks + 1, nenv, self.nq), **o)
-            res.qvel_hist = torch.zeros((nticks + 1, nenv, self.nv), **o)
-            res.tau_hist = torch.zeros((nticks, nenv, d["nu"]), **o)
-            res.status_hist = torch.zeros((nticks, nenv), device=self.device, dtype=torch.int32)
-            a.qpos_hist, a.qvel_hist = res.qpos_hist.data_ptr(), res.qvel_hist.data_ptr()
-            a.tau_hist, a.status_hist = res.tau_hist.data_ptr(), res.status_hist.data_ptr()
-        pl = None
-        if plant is not None:
-            pl, pkeep = self._plant_block(plant, res, nenv, nticks, history)
-            keep += [pl] + pkeep
-        if isinstance(workspace, str):
-            workspace = torch.empty((max(self.rollout_workspace_bytes(
-                solver, nenv, nticks, env=env, plant=pl is not None) // 8, 2),), **o)
-        if workspace is not None:
-            a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
         a.qpos, a.qvel = qpos.data_ptr(), qvel.data_ptr()
         a.tau, a.bad_ticks = res.tau.data_ptr(), res.bad_ticks.data_ptr()
         s = ctypes.c_void_p(self._stream(stream, self.device))
+        scp = ctypes.byref(sc) if sc is not None else None
+        head = (solver._h, self._h, nenv, ctypes.byref(a))
+        if pl is not None:
+            entry, tail = "osc_batch_rollout_plant", (scp, ep, kp, ctypes.byref(pl), s)
+        elif sc is not None:
+            entry, tail = "osc_batch_rollout_sched", (scp, ep, kp, s)
+        elif env:
+            entry, tail = "osc_batch_rollout_env", (ep, kp, s)
+        else:
+            entry, tail = "osc_batch_rollout", (s,)
         with torch.cuda.device(self.device):
-            if pl is not None:
-                rc = _lib.lib().osc_batch_rollout_plant(solver._h, self._h, nenv, ctypes.byref(a),
-                                                        ctypes.byref(sc), ep, kp,
-                                                        ctypes.byref(pl), s)
-            else:
-                rc = _lib.lib().osc_batch_rollout_sched(solver._h, self._h, nenv, ctypes.byref(a),
-                                                        ctypes.byref(sc), ep, kp, s)
+            rc = getattr(_lib.lib(), entry)(*head, *tail)
         if rc != 0:
-            raise _lib.OSCError("osc_batch_rollout_plant" if pl is not None else
-                                "osc_batch_rollout_sched", rc)
+            raise _lib.OSCError(entry, rc)
         res._keep = keep + [workspace]   # inputs and scratch stay alive until the stream is done
         return res
 
@@ -825,13 +761,10 @@ class KinematicsBatch:
                 "the matched model's would be wrong for it")
         want = tuple(want)
         sched_call = schedule is not None or any(w in self.ROLLOUT_SCHEDULE_GRADS for w in want)
-        if sched_call:
-            if T is not None and pd is not None:
-                raise ValueError("at most one of T and pd may be given")
-            if T is None and pd is None and (schedule is None or schedule.T is None):
-                raise ValueError("one of T, pd and schedule.T must be given")
-        elif (T is None) == (pd is None):
-            raise ValueError("exactly one of T and pd must be given")
+        if T is not None and pd is not None:
+            raise ValueError("at most one of T and pd may be given")
+        if T is None and pd is None and (schedule is None or schedule.T is None):
+            raise ValueError("one of T, pd and schedule.T must be given")
         if result.qpos_hist is None or result.qvel_hist is None or result.status_hist is None:
             raise ValueError("rollout_backward: the forward call needs history=True")
         for w in want:
@@ -860,30 +793,7 @@ class KinematicsBatch:
         ep, kp, blocks = self._blocks(solver, env_params, kin_params, nenv) if env else \
             (None, None, [])
         keep += blocks
-        if sched_call and pd is not None:
-            keep += list(self._pd_args(a, pd, nenv, per_env_seq).values())
-        elif sched_call:
-            a.target_mode = _lib.ROLLOUT_TARGETS_HELD
-            if T is not None:
-                T = self._dev(T, (nenv, d["ns"], 6), "T")
-                a.T = T.data_ptr()
-                keep.append(T)
-        elif T is not None:
-            T = self._dev(T, (nenv, d["ns"], 6), "T")
-            a.target_mode, a.T = _lib.ROLLOUT_TARGETS_HELD, T.data_ptr()
-            keep.append(T)
-        else:
-            pos_ref, quat_ref, gains = pd
-            pos_ref, quat_ref = (r if isinstance(r, torch.Tensor) else
-                                 np.asarray(r, dtype=np.float64) for r in (pos_ref, quat_ref))
-            per_env = [int(r.ndim == 2) for r in (pos_ref, quat_ref)]
-            pos_ref = self._dev(pos_ref, (nenv, 3) if per_env[0] else (3,), "pos_ref")
-            quat_ref = self._dev(quat_ref, (nenv, 4) if per_env[1] else (4,), "quat_ref")
-            a.target_mode = _lib.ROLLOUT_TARGETS_PD_BASE
-            a.pos_ref, a.pos_ref_per_env = pos_ref.data_ptr(), per_env[0]
-            a.quat_ref, a.quat_ref_per_env = quat_ref.data_ptr(), per_env[1]
-            a.gains[:] = [float(g) for g in gains]
-            keep += [pos_ref, quat_ref]
+        keep += self._target_args(a, T, pd, nenv, d, per_env_seq)
         hq = self._grad_tensor(result.qpos_hist, (nticks + 1, nenv, self.nq), "qpos_hist")
         hv = self._grad_tensor(result.qvel_hist, (nticks + 1, nenv, self.nv), "qvel_hist")
         hs = self._grad_tensor(result.status_hist, (nticks, nenv), "status_hist", torch.int32)

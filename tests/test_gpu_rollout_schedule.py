@@ -32,6 +32,7 @@ import test_rollout_schedule_ref as scpu
 from guard import assert_guards_intact, guarded, guarded_like
 from osc_amd import _lib
 from osc_amd.kinematics import KinEnvParams, RolloutSchedule, random_states
+from osc_amd.solver import EnvParams
 from osc_amd.synth import generate
 
 pytestmark = pytest.mark.gpu
@@ -226,6 +227,45 @@ def test_reductions_to_the_plain_rollout(gpu, mode, warm):
             assert torch.equal(r.tau, plain.tau)
         if nticks == 0:
             assert torch.equal(empty.qpos, dev(c["qpos"])) and empty.qpos_hist.shape[0] == 1
+
+
+@pytest.mark.parametrize("mode", ["held", "pd"])
+@pytest.mark.parametrize("robot,nenv", [(GO2, 17), (WALTER, 5)])
+def test_backward_reductions_to_the_plain_backward(gpu, robot, nenv, mode):
+    """The backward's reduction: osc_batch_rollout_backward and osc_batch_rollout_backward_sched
+    on one forward (tb.case's inputs, K = 3, per-env mass scales, task weights and force caps),
+    the second with the held mask tiled K times as its schedule and no held mask, the same
+    cotangents on all three histories: every gradient the plain entry gives -- qpos0, qvel0, T
+    (held targets), env.w_pos, env.fz_ub, kin.mass_scale -- bitwise equal.  17 Go2 envs are one
+    full 16-env block and a one-env tail."""
+    tree, kb, km, s, mdl = pair(robot)
+    c = tb.case(robot)
+    rows = slice(0, nenv)
+    rng = np.random.default_rng(5)
+    ep = EnvParams(w_pos=dev(np.asarray(mdl.w_pos) * rng.uniform(0.5, 2.0, (nenv, mdl.ns))),
+                   fz_ub=dev(float(mdl.z_ub[2]) * rng.uniform(0.6, 1.2, nenv)))
+    kp = KinEnvParams(mass_scale=dev(c["ms"][rows]))
+    kw = dict(T=c["T"][rows]) if mode == "held" else \
+        dict(pd=(c["pos_ref"][rows], c["quat_ref"], GAINS))
+    mask = c["mask"][rows]
+    res = kb.rollout(s, c["qpos"][rows], c["qvel"][rows], mask, K, DT, warm=False, history=True,
+                     env_params=ep, kin_params=kp, **kw)
+    want = ("qpos0", "qvel0", "env.w_pos", "env.fz_ub", "kin.mass_scale") + \
+        (("T",) if mode == "held" else ())
+    bw = dict(grad_qpos_hist=dev(c["cot"]["qpos"][:, rows]),
+              grad_qvel_hist=dev(c["cot"]["qvel"][:, rows]),
+              grad_tau_hist=dev(c["cot"]["tau"][:, rows]), env_params=ep, kin_params=kp,
+              want=want, **kw)
+    plain = kb.rollout_backward(s, res, mask, DT, **bw)
+    tiled = np.broadcast_to(mask, (K,) + mask.shape).copy()
+    sched = kb.rollout_backward(s, res, None, DT, schedule=RolloutSchedule(mask=tiled), **bw)
+    torch.cuda.synchronize()
+    assert set(plain) == set(sched) == set(want)
+    for k in want:
+        assert torch.isfinite(plain[k]).all(), k
+        assert bitwise(plain[k].cpu().numpy(), sched[k].cpu().numpy()), k
+    if robot == GO2:
+        assert all(plain[k].abs().max() > 0 for k in ("qpos0", "qvel0", "kin.mass_scale"))
 
 
 # ---- the backward's shared case: NBIG envs, K ticks ----------------------------------------------------

@@ -13,7 +13,7 @@ every entry solves the same problems and the differences are the interface's own
   e_bwd_held_seq       ..._backward_sched, T and the mask from the schedule, grad_T_seq as well
   e_bwd_pd             osc_batch_rollout_backward, PD targets -> grad_qpos0, grad_qvel0
   e_bwd_pd_seq         ..._backward_sched on d's forward -> also grad_T_seq, grad_pos_ref_seq,
-                       grad_quat_ref, grad_gains (the scheduled combine, and the recompute's addition)
+                       grad_quat_ref, grad_gains (the combine's schedule outputs, and the recompute's addition)
 One JSON line per size.
 
     python tools/rollout_schedule_timing.py   (ROLLOUT_SCHED_SIZES="4096,65536", ROLLOUT_SCHED_ROUNDS=5)
