@@ -16,10 +16,11 @@
  * still no ground.
  *
  * Out of scope: gradients through the plant (osc_batch_rollout_backward of a plant rollout would
- * be the matched model's); a wrench on an arbitrary body (the caller forms J' f and passes it as
- * qfrc_applied); contact forces as constraint reactions, or any ground; the two-model grids
- * (osc_mixed.h), the host feeds (osc_host_feed.h) and the controller shim (osc_controller.h);
- * models with wheel rows.
+ * be the matched model's; they are osc_plant_backward.h's: the forward dynamics' vector-Jacobian
+ * product and osc_batch_rollout_plant_backward); a wrench on an arbitrary body (the caller forms
+ * J' f and passes it as qfrc_applied); contact forces as constraint reactions, or any ground; the
+ * two-model grids (osc_mixed.h), the host feeds (osc_host_feed.h) and the controller shim
+ * (osc_controller.h); models with wheel rows.
  */
 #ifndef OSC_PLANT_H_
 #define OSC_PLANT_H_

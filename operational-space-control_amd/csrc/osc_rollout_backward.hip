@@ -16,7 +16,8 @@
 //                 rates (staged in LDS, as the forward stages the states), and so do the three
 //                 lanes of its rates: every one of those seven lanes recomputes the quaternion's
 //                 adjoint and keeps its own output -- one owning lane per output, no atomics.
-//   combine       g[t] = step-direct + kinematics + PD + cotangent of slab t, in that order; the
+//   combine       g[t] = step-direct + kinematics (+ the plant's kinematics, osc_plant_backward.h)
+//                 + PD + cotangent of slab t, in that order; the
 //                 tick-ordered sums of the target and parameter gradients; in PD mode the packed
 //                 base state of slab t - 1 for the next tick's producer call.  The same launch
 //                 writes what a scheduled call asks for, each behind a NULL check: tick t's
@@ -47,7 +48,12 @@ using osc_kin::KinDev;
 static_assert(sizeof(void*) != 8 || sizeof(osc_rollout_backward_args) == 208,
               "osc_rollout_backward_args layout");
 
-constexpr int kMaxAcc = 11;   // grad_T, seven osc_env_grads fields, three osc_kin_env_grads fields
+// grad_T, seven osc_env_grads fields, three osc_kin_env_grads fields; with a plant
+// (osc_plant_backward.h) its held grad_qfrc_applied and its own three osc_kin_env_grads fields
+constexpr int kMaxAcc = 15;
+
+static_assert(sizeof(void*) != 8 || sizeof(osc_rollout_plant_backward) == 56,
+              "osc_rollout_plant_backward layout");
 
 // a (x) b, quaternions (w, x, y, z)
 __device__ __forceinline__ void quat_mul(const double* a, const double* b, double* o) {
@@ -207,6 +213,8 @@ struct CombineArgs {
   double* gv;
   const double* kq;           // the kinematics' backward's grad_qpos / grad_qvel
   const double* kv;
+  const double* kq2;          // the PLANT's kinematics' backward's (osc_plant_backward.h), nullable
+  const double* kv2;
   const double* hq;           // slab t of grad_qpos_hist / grad_qvel_hist, nullable
   const double* hv;
   const double* gT;           // this tick's grad_T [nenv][ns][6]; NULL = not formed
@@ -249,6 +257,7 @@ __global__ __launch_bounds__(kBlock) void osc_rollout_combine_kernel(CombineArgs
     const int el = idx / nq, i = idx - el * nq;
     const long long g = e0 * nq + idx, e = e0 + el;
     double v = a.gq[g] + a.kq[g];
+    if (a.kq2) v += a.kq2[g];
     if (pd && i < 7) {   // free root: qpos[0:3] position, qpos[3:7] quaternion
       const double* t = a.gT + e * trow;
       if (i < 3) {
@@ -270,6 +279,7 @@ __global__ __launch_bounds__(kBlock) void osc_rollout_combine_kernel(CombineArgs
     const int el = idx / nv, d = idx - el * nv;
     const long long g = e0 * nv + idx, e = e0 + el;
     double v = a.gv[g] + a.kv[g];
+    if (a.kv2) v += a.kv2[g];
     if (pd && d < 6) v += -(d < 3 ? a.kd_lin : a.kd_ang) * a.gT[e * trow + d];
     if (a.hv) v += a.hv[g];
     a.gv[g] = v;
@@ -309,6 +319,30 @@ __global__ __launch_bounds__(kBlock) void osc_rollout_combine_kernel(CombineArgs
       } else {
         out[e * 4 + (j - 7)] += r;
       }
+    }
+  }
+}
+
+// The plant's cotangents into the solve's (osc_plant_backward.h, step 7), one flat launch: per env
+// grad_Jc onto the contact rows [r0, r0 + nz) of gJ and, when the plant shares the controller's
+// parameters (gMp non-NULL), grad_M_p onto gM and grad_C_p onto gC.  One owning thread per entry.
+__global__ __launch_bounds__(kBlock) void osc_rollout_plant_route_kernel(
+    long long nenv, int nv, int srows, int r0, int nz, const double* __restrict__ gJc,
+    double* __restrict__ gJ, const double* __restrict__ gMp, double* __restrict__ gM,
+    const double* __restrict__ gCp, double* __restrict__ gC) {
+  const long long nj = static_cast<long long>(nz) * nv, nm = static_cast<long long>(nv) * nv;
+  const long long per = nj + (gMp ? nm + nv : 0), total = nenv * per;
+  for (long long idx = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; idx < total;
+       idx += static_cast<long long>(gridDim.x) * kBlock) {
+    const long long e = idx / per;
+    long long r = idx - e * per;
+    if (r < nj) {
+      gJ[e * srows * nv + static_cast<long long>(r0) * nv + r] += gJc[e * nj + r];
+    } else if ((r -= nj) < nm) {
+      gM[e * nm + r] += gMp[e * nm + r];
+    } else {
+      r -= nm;
+      gC[e * nv + r] += gCp[e * nv + r];
     }
   }
 }
@@ -360,7 +394,8 @@ int launch_step_adjoint(const StepAdjArgs& a, hipStream_t s) {
 }
 
 constexpr int kEnvFields = 7, kKinFields = 3;
-static_assert(1 + kEnvFields + kKinFields <= kMaxAcc, "CombineArgs holds every running sum");
+static_assert(1 + kEnvFields + kKinFields + 1 + kKinFields <= kMaxAcc,
+              "CombineArgs holds every running sum");
 
 struct BackwardWorkspace {   // sections, each 256-B aligned (byte offsets)
   size_t M, C, J, b, T, x, y, tau, status, gx, gM, gC, gJ, gb, gT, gq, gv, kq, kv, bpos, bquat,
@@ -421,6 +456,36 @@ struct BackwardWorkspace {   // sections, each 256-B aligned (byte offsets)
     qp_bytes = 0;
     if (rc == OSC_OK) rc = osc_workspace_bytes(model, nenv, &qp_bytes);
     total = qp + align256(qp_bytes);
+  }
+};
+
+// The plant's sections behind the backward's own (include/osc_plant_backward.h), each 256-B
+// aligned: the plant's M_p | C_p, the recomputed qacc, the step's grad_qacc, the forward dynamics'
+// grad_M_p | grad_C_p | grad_Jc | grad_qfrc, the plant's kinematics' state adjoints and one tick's
+// plant parameter gradients.
+struct PlantBackwardWorkspace {
+  size_t mp, cp, qacc, gacc, gmp, gcp, gjc, gf, kq, kv, kg[kKinFields], total;
+  PlantBackwardWorkspace(const BackwardWorkspace& L, const KinDev& k, const osc_model_desc& d,
+                         int32_t nenv) {
+    const size_t n = static_cast<size_t>(nenv), dbl = sizeof(double), nv = d.nv;
+    size_t off = L.total;
+    auto take = [&](size_t bytes) {
+      const size_t at = off;
+      off += align256(bytes);
+      return at;
+    };
+    mp = take(dbl * n * nv * nv);
+    cp = take(dbl * n * nv);
+    qacc = take(dbl * n * nv);
+    gacc = take(dbl * n * nv);
+    gmp = take(dbl * n * nv * nv);
+    gcp = take(dbl * n * nv);
+    gjc = take(dbl * n * 3 * d.nc * nv);
+    gf = take(dbl * n * nv);
+    kq = take(dbl * n * k.nq);
+    kv = take(dbl * n * nv);
+    for (int i = 0; i < kKinFields; ++i) kg[i] = take(dbl * n * L.kg_cnt[i]);
+    total = off;
   }
 };
 
@@ -508,7 +573,32 @@ extern "C" int osc_batch_rollout_backward(const osc_model* model, const osc_kin_
                                           int32_t nenv, const osc_rollout_backward_args* args,
                                           const osc_env_params* ep, const osc_kin_env_params* kp,
                                           void* stream) {
-  return osc::rollout_backward_run(model, kin, nenv, args, nullptr, nullptr, ep, kp, stream);
+  return osc::rollout_backward_run(model, kin, nenv, args, nullptr, nullptr, ep, kp, nullptr,
+                                   stream);
+}
+
+// ---- the backward pass through a plant (include/osc_plant_backward.h) ----
+
+extern "C" int osc_rollout_plant_backward_workspace_bytes(const osc_model* model,
+                                                          const osc_kin_model* kin, int32_t nenv,
+                                                          size_t* bytes) {
+  if (!bytes || nenv < 0) return OSC_ERR_INVALID_ARGUMENT;
+  osc_model_desc d;
+  const int rc = check_handles(model, kin, &d);
+  if (rc != OSC_OK) return rc;
+  const BackwardWorkspace L(model, kin, d, nenv);
+  if (L.rc != OSC_OK) return L.rc;
+  *bytes = PlantBackwardWorkspace(L, kin->host, d, nenv).total;
+  return OSC_OK;
+}
+
+extern "C" int osc_batch_rollout_plant_backward(
+    const osc_model* model, const osc_kin_model* kin, int32_t nenv,
+    const osc_rollout_backward_args* args, const osc_rollout_schedule* sched,
+    const osc_rollout_schedule_grads* sched_grads, const osc_env_params* env_params,
+    const osc_kin_env_params* kin_params, const osc_rollout_plant_backward* plant, void* stream) {
+  return osc::rollout_backward_run(model, kin, nenv, args, sched, sched_grads, env_params,
+                                   kin_params, plant, stream);
 }
 
 // osc_batch_rollout_backward (sched and sgrads NULL) and osc_batch_rollout_backward_sched
@@ -518,7 +608,8 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
                               const osc_rollout_backward_args* args,
                               const osc_rollout_schedule* sched,
                               const osc_rollout_schedule_grads* sgrads, const osc_env_params* ep,
-                              const osc_kin_env_params* kp, void* stream) {
+                              const osc_kin_env_params* kp,
+                              const osc_rollout_plant_backward* plant, void* stream) {
   // ---- every check before the first launch ----
   osc_model_desc d;
   int rc = check_handles(model, kin, &d);
@@ -578,7 +669,41 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
         static_cast<const void*>(sg.grad_quat_ref), static_cast<const void*>(sg.grad_pos_ref_seq),
         static_cast<const void*>(sg.grad_quat_ref_seq), static_cast<const void*>(sg.grad_gains)})
     if (!aligned8(p)) return OSC_ERR_INVALID_ARGUMENT;
-  if (!args->grad_qpos0 && !args->grad_qvel0 && !args->grad_T && !any_eg && !any_kg && !any_sg)
+  // ---- the plant (osc_plant_backward.h): NULL = every branch below takes its old side ----
+  const bool with_plant = plant != nullptr;
+  const osc_kin_env_params* pkp = with_plant ? plant->kin_params : nullptr;
+  const bool plant_kin =
+      pkp != nullptr && (pkp->mass_scale || pkp->com_offset || pkp->armature_scale);
+  double* pkg_out[kKinFields] = {};
+  bool any_pkg = false;
+  if (with_plant) {
+    for (const void* p : {static_cast<const void*>(plant->qfrc_applied),
+                          static_cast<const void*>(plant->qfrc_applied_seq),
+                          static_cast<const void*>(plant->grad_qacc_hist),
+                          static_cast<const void*>(plant->grad_qfrc_applied),
+                          static_cast<const void*>(plant->grad_qfrc_applied_seq)})
+      if (!aligned8(p)) return OSC_ERR_INVALID_ARGUMENT;
+    if (pkp != nullptr)
+      for (const double* a : {pkp->mass_scale, pkp->com_offset, pkp->armature_scale})
+        if (!aligned8(a)) return OSC_ERR_INVALID_ARGUMENT;
+    if (plant->kin_grads) {
+      const osc_kin_env_grads& g = *plant->kin_grads;
+      double* f[kKinFields] = {g.mass_scale, g.com_offset, g.armature_scale};
+      for (int i = 0; i < kKinFields; ++i) {
+        pkg_out[i] = f[i];
+        any_pkg = any_pkg || f[i] != nullptr;
+        if (!aligned8(f[i])) return OSC_ERR_INVALID_ARGUMENT;
+      }
+    }
+    if (any_pkg && !plant_kin) return OSC_ERR_INVALID_ARGUMENT;
+    if (plant->grad_qfrc_applied && plant->qfrc_applied_seq) return OSC_ERR_INVALID_ARGUMENT;
+    if (plant->grad_qfrc_applied_seq && !plant->qfrc_applied_seq) return OSC_ERR_INVALID_ARGUMENT;
+    // (the forward dynamics and its backward refuse a model with wheel rows: check_handles did)
+  }
+  const bool any_pl =
+      with_plant && (plant->grad_qfrc_applied || plant->grad_qfrc_applied_seq || any_pkg);
+  if (!args->grad_qpos0 && !args->grad_qvel0 && !args->grad_T && !any_eg && !any_kg && !any_sg &&
+      !any_pl)
     return OSC_ERR_INVALID_ARGUMENT;
   for (const void* p :
        {static_cast<const void*>(args->T), static_cast<const void*>(args->pos_ref),
@@ -600,7 +725,9 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
   if ((reinterpret_cast<uintptr_t>(args->workspace) & 15u) != 0) return OSC_ERR_INVALID_ARGUMENT;
   const BackwardWorkspace L(model, kin, d, nenv);
   if (L.rc != OSC_OK) return L.rc;
-  if (args->workspace && args->workspace_bytes < L.total) return OSC_ERR_INVALID_ARGUMENT;
+  const PlantBackwardWorkspace LP(L, k, d, nenv);   // (offsets only; used with a plant alone)
+  const size_t ws_total = with_plant ? LP.total : L.total;
+  if (args->workspace && args->workspace_bytes < ws_total) return OSC_ERR_INVALID_ARGUMENT;
   if (k.nq > kMaxNq || k.nv > OSC_KIN_MAX_DOFS || k.nbody > OSC_KIN_MAX_BODIES)
     return OSC_ERR_INVALID_ARGUMENT;
 
@@ -619,6 +746,10 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
   if (rc == OSC_OK && sg.grad_pos_ref) rc = ok(hipMemsetAsync(sg.grad_pos_ref, 0, dbl * n * 3, s));
   if (rc == OSC_OK && sg.grad_quat_ref) rc = ok(hipMemsetAsync(sg.grad_quat_ref, 0, dbl * n * 4, s));
   if (rc == OSC_OK && sg.grad_gains) rc = ok(hipMemsetAsync(sg.grad_gains, 0, dbl * n * 4, s));
+  if (rc == OSC_OK && with_plant && plant->grad_qfrc_applied)
+    rc = ok(hipMemsetAsync(plant->grad_qfrc_applied, 0, dbl * n * nv, s));
+  for (int i = 0; i < kKinFields && rc == OSC_OK; ++i)
+    if (pkg_out[i]) rc = ok(hipMemsetAsync(pkg_out[i], 0, dbl * n * L.kg_cnt[i], s));
   if (rc != OSC_OK) return rc;
 
   auto seed = [&](double* out, const double* hist, size_t row) {   // slab nticks' cotangent
@@ -637,7 +768,7 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
   char* base = static_cast<char*>(args->workspace);
   bool owned = false;
   if (base == nullptr) {
-    if (hipMallocAsync(reinterpret_cast<void**>(&base), L.total, s) != hipSuccess)
+    if (hipMallocAsync(reinterpret_cast<void**>(&base), ws_total, s) != hipSuccess)
       return OSC_ERR_DEVICE;
     owned = true;
   }
@@ -656,6 +787,12 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
     for (int i = 0; i < kEnvFields; ++i) *ef[i] = eg_out[i] ? dptr(L.eg[i]) : nullptr;
     double** kf[kKinFields] = {&kg_tick.mass_scale, &kg_tick.com_offset, &kg_tick.armature_scale};
     for (int i = 0; i < kKinFields; ++i) *kf[i] = kg_out[i] ? dptr(L.kg[i]) : nullptr;
+  }
+  osc_kin_env_grads pkg_tick{};   // the plant's
+  {
+    double** kf[kKinFields] = {&pkg_tick.mass_scale, &pkg_tick.com_offset,
+                               &pkg_tick.armature_scale};
+    for (int i = 0; i < kKinFields; ++i) *kf[i] = pkg_out[i] ? dptr(LP.kg[i]) : nullptr;
   }
 
   rc = seed(gq, args->grad_qpos_hist, nq);
@@ -689,6 +826,27 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
             : osc_batch_solve_ex(model, nenv, M, C, J, b, T, mask, &ex, dptr(L.tau),
                                  x, status, nullptr, base + L.qp, L.qp_bytes, stream);
     if (rc != OSC_OK) break;
+    // ---- with a plant: its M_p, C_p (its own parameters) or the tick's, then its qacc ----
+    const double* Mp = M;
+    if (with_plant) {
+      const double* Cp = C;
+      if (plant_kin) {
+        // (the kernel wants J and b too; they land in the gJ / gb sections, which the solve's
+        // backward overwrites later, so that an env with invalid PLANT parameters keeps the
+        // controller's J and b for its solve's backward)
+        rc = osc_batch_kinematics_env(kin, nenv, qpos, qvel, pkp, dptr(LP.mp), dptr(LP.cp),
+                                      dptr(L.gJ), dptr(L.gb), nullptr, stream);
+        if (rc != OSC_OK) break;
+        Mp = dptr(LP.mp);
+        Cp = dptr(LP.cp);
+      }
+      const double* qfrc = plant->qfrc_applied_seq ? plant->qfrc_applied_seq + n * nv * t
+                                                   : plant->qfrc_applied;
+      rc = osc_batch_forward_dynamics(model, nenv, Mp, Cp, J, x + nv, static_cast<int64_t>(nx),
+                                      x + nv + nu, static_cast<int64_t>(nx), qfrc, dptr(LP.qacc),
+                                      stream);
+      if (rc != OSC_OK) break;
+    }
     // ---- the step's adjoint: grad_x, and the direct part of slab t's adjoints in place ----
     StepAdjArgs a{};
     a.K = kin->dev;
@@ -711,8 +869,35 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
     a.ntail = static_cast<int32_t>(nx - nv);
     a.nu = d.nu;
     a.gtau = args->grad_tau_hist ? args->grad_tau_hist + n * nu * t : nullptr;
+    if (with_plant) {   // the step integrated qacc; grad_qacc goes to a buffer of its own, and the
+      a.qacc = dptr(LP.qacc);   // forward dynamics' backward writes the whole grad_x row
+      a.qacc_stride = static_cast<int64_t>(nv);
+      a.gacc = dptr(LP.gacc);
+      a.gacc_stride = static_cast<int64_t>(nv);
+      a.ntail = 0;
+      a.gtau = nullptr;
+    }
     rc = launch_step_adjoint(a, s);
     if (rc != OSC_OK) break;
+    if (with_plant) {
+      // grad_x = (0, grad_tau_hist[t] + w[nb:], Jc w); the plant-side cotangents; w itself into
+      // grad_qfrc_applied_seq[t] or the held sum's term
+      FdBackwardExtras ex{};
+      ex.grad_qacc_add = plant->grad_qacc_hist ? plant->grad_qacc_hist + n * nv * t : nullptr;
+      ex.grad_tau = args->grad_tau_hist ? args->grad_tau_hist + n * nu * t : nullptr;
+      ex.status = args->status_hist + n * t;
+      ex.grad_x_dv = dptr(L.gx);
+      ex.grad_x_stride = static_cast<int64_t>(nx);
+      double* gf = plant->grad_qfrc_applied_seq ? plant->grad_qfrc_applied_seq + n * nv * t
+                   : plant->grad_qfrc_applied   ? dptr(LP.gf)
+                                                : nullptr;
+      rc = forward_dynamics_backward_run(
+          model, nenv, Mp, J, x + nv + nu, static_cast<int64_t>(nx), dptr(LP.qacc), dptr(LP.gacc),
+          static_cast<int64_t>(nv), dptr(LP.gmp), dptr(LP.gcp), dptr(LP.gjc), dptr(L.gx) + nv,
+          static_cast<int64_t>(nx), dptr(L.gx) + nv + nu, static_cast<int64_t>(nx), gf, &ex,
+          stream);
+      if (rc != OSC_OK) break;
+    }
     // ---- the solve's backward, then the kinematics' ----
     double* gT = want_gT ? dptr(L.gT) : nullptr;
     rc = env_bwd ? osc_batch_solve_backward_env(model, nenv, M, J, b, T, mask, ep, x,
@@ -725,10 +910,26 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
                                                  dptr(L.gC), dptr(L.gJ), nullptr, gT, dptr(L.gb),
                                                  base + L.qp, L.qp_bytes, stream);
     if (rc != OSC_OK) break;
+    if (with_plant) {   // the plant's cotangents onto the solve's (they were formed before it ran)
+      const long long per = 3LL * d.nc * nv + (plant_kin ? 0 : nv * nv + nv);
+      hipLaunchKernelGGL(osc_rollout_plant_route_kernel, dim3(grid_for(per * nenv)), dim3(kBlock),
+                         0, s, static_cast<long long>(nenv), static_cast<int>(nv),
+                         static_cast<int>(s6), 3 * d.ns - 3 * d.nc, 3 * d.nc, dptr(LP.gjc),
+                         dptr(L.gJ), plant_kin ? nullptr : dptr(LP.gmp), dptr(L.gM),
+                         plant_kin ? nullptr : dptr(LP.gcp), dptr(L.gC));
+      rc = ok(hipGetLastError());
+      if (rc != OSC_OK) break;
+    }
     rc = osc_batch_kinematics_backward(kin, nenv, qpos, qvel, kp, dptr(L.gM), dptr(L.gC),
                                        dptr(L.gJ), dptr(L.gb), nullptr, dptr(L.kq), dptr(L.kv),
                                        any_kg ? &kg_tick : nullptr, stream);
     if (rc != OSC_OK) break;
+    if (plant_kin) {   // the plant's own parameters: its state adjoints and parameter gradients
+      rc = osc_batch_kinematics_backward(kin, nenv, qpos, qvel, pkp, dptr(LP.gmp), dptr(LP.gcp),
+                                         nullptr, nullptr, nullptr, dptr(LP.kq), dptr(LP.kv),
+                                         any_pkg ? &pkg_tick : nullptr, stream);
+      if (rc != OSC_OK) break;
+    }
     // ---- combine: slab t's adjoints, the tick-ordered sums, the next tick's base state ----
     // (the plain entry has no schedule gradient: sg's pointers are NULL, and so are c's)
     CombineArgs c{};
@@ -779,6 +980,17 @@ int osc::rollout_backward_run(const osc_model* model, const osc_kin_model* kin, 
       if (kg_out[i])
         c.acc[c.nacc++] =
             CombineAcc{kg_out[i], dptr(L.kg[i]), static_cast<int32_t>(L.kg_cnt[i])};
+    if (plant_kin) {
+      c.kq2 = dptr(LP.kq);
+      c.kv2 = dptr(LP.kv);
+    }
+    if (with_plant && plant->grad_qfrc_applied)
+      c.acc[c.nacc++] =
+          CombineAcc{plant->grad_qfrc_applied, dptr(LP.gf), static_cast<int32_t>(nv)};
+    for (int i = 0; i < kKinFields; ++i)
+      if (pkg_out[i])
+        c.acc[c.nacc++] =
+            CombineAcc{pkg_out[i], dptr(LP.kg[i]), static_cast<int32_t>(L.kg_cnt[i])};
     hipLaunchKernelGGL(osc_rollout_combine_kernel, dim3(env_blocks(nenv)), dim3(kBlock), 0, s, c);
     rc = ok(hipGetLastError());
   }

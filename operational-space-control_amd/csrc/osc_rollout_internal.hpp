@@ -15,6 +15,7 @@
 #include "osc_kin_device.hpp"
 #include "osc_kinematics.h"
 #include "osc_plant.h"
+#include "osc_plant_backward.h"
 #include "osc_rollout_schedule.h"
 
 namespace osc {
@@ -146,12 +147,30 @@ int rollout_run(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
                 const osc_env_params* ep, const osc_kin_env_params* kp,
                 const osc_rollout_plant* plant, void* stream);
 
-// osc_rollout_backward.hip: behind osc_batch_rollout_backward (sched and sgrads NULL) and
-// osc_batch_rollout_backward_sched
+// osc_rollout_backward.hip: behind osc_batch_rollout_backward (sched, sgrads and plant NULL),
+// osc_batch_rollout_backward_sched (plant NULL) and osc_batch_rollout_plant_backward
 int rollout_backward_run(const osc_model* model, const osc_kin_model* kin, int32_t nenv,
                          const osc_rollout_backward_args* args, const osc_rollout_schedule* sched,
                          const osc_rollout_schedule_grads* sgrads, const osc_env_params* ep,
-                         const osc_kin_env_params* kp, void* stream);
+                         const osc_kin_env_params* kp, const osc_rollout_plant_backward* plant,
+                         void* stream);
+
+// osc_forward_dynamics_backward.hip: osc_batch_forward_dynamics_backward (extras NULL) and, for
+// the rollout's backward, the same launch completing the solve's grad_x row.  Not in the C ABI.
+struct FdBackwardExtras {
+  const double* grad_qacc_add;   // [nenv][nv], nullable: added to grad_qacc (grad_qacc_hist[t])
+  const double* grad_tau;        // [nenv][nu], nullable: added to w[nb:] in grad_u (needs grad_u)
+  const int32_t* status;         // [nenv], nullable: OSC_SOLVE_NUMERICAL makes the env bad
+  double* grad_x_dv;             // nullable: rows of nv zeros at grad_x_dv + e * grad_x_stride
+  int64_t grad_x_stride;
+};
+int forward_dynamics_backward_run(const osc_model* model, int32_t nenv, const double* M,
+                                  const double* J, const double* z, int64_t z_stride,
+                                  const double* qacc, const double* grad_qacc,
+                                  int64_t grad_qacc_stride, double* grad_M, double* grad_C,
+                                  double* grad_Jc, double* grad_u, int64_t grad_u_stride,
+                                  double* grad_z, int64_t grad_z_stride, double* grad_qfrc,
+                                  const FdBackwardExtras* extras, void* stream);
 
 // ---- one tick's inputs (osc_rollout_schedule.hip) ----
 // The backward recomputes the forward's tick, so both loops resolve a tick's inputs through

@@ -159,5 +159,5 @@ extern "C" int osc_batch_rollout_backward_sched(const osc_model* model, const os
                                                 const osc_kin_env_params* kin_params,
                                                 void* stream) {
   return osc::rollout_backward_run(model, kin, nenv, bargs, sched, sgrads, env_params, kin_params,
-                                   stream);
+                                   nullptr, stream);
 }

@@ -81,6 +81,11 @@ ROLLOUT_SCHEDULE_SYMBOLS = ("osc_batch_rollout_sched", "osc_pd_base_targets_back
 # tests/test_plant_ref.py pins this list to that header's declarations.
 PLANT_SYMBOLS = ("osc_batch_forward_dynamics", "osc_rollout_plant_workspace_bytes",
                  "osc_batch_rollout_plant")
+# include/osc_plant_backward.h (the forward dynamics' vector-Jacobian product), apart likewise;
+# tests/test_plant_backward_ref.py pins this list to that header's declarations.
+PLANT_BACKWARD_SYMBOLS = ("osc_batch_forward_dynamics_backward",
+                          "osc_rollout_plant_backward_workspace_bytes",
+                          "osc_batch_rollout_plant_backward")
 
 OSC_KIN_MAX_BODIES = 16
 OSC_KIN_MAX_DOFS = 32
@@ -256,6 +261,15 @@ class OscRolloutPlant(ctypes.Structure):
                 ("qfrc_applied_seq", ctypes.c_void_p), ("qacc_hist", ctypes.c_void_p)]
 
 
+class OscRolloutPlantBackward(ctypes.Structure):
+    """osc_rollout_plant_backward (include/osc_plant_backward.h)."""
+    _fields_ = [("kin_params", ctypes.POINTER(OscKinEnvParams)), ("qfrc_applied", ctypes.c_void_p),
+                ("qfrc_applied_seq", ctypes.c_void_p), ("grad_qacc_hist", ctypes.c_void_p),
+                ("grad_qfrc_applied", ctypes.c_void_p),
+                ("grad_qfrc_applied_seq", ctypes.c_void_p),
+                ("kin_grads", ctypes.POINTER(OscKinEnvGrads))]
+
+
 FEED_QP, FEED_JOINT_STATES, FEED_WARM = 0, 1, 1
 
 
@@ -424,6 +438,15 @@ def lib() -> ctypes.CDLL:
     L.osc_batch_rollout_plant.argtypes = [vp, vp, i32, ctypes.POINTER(OscRolloutArgs), scp, ep,
                                           kep, ctypes.POINTER(OscRolloutPlant), vp]
     for name in PLANT_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
+    i64 = ctypes.c_int64
+    L.osc_batch_forward_dynamics_backward.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp, i64, vp,
+                                                      vp, vp, vp, i64, vp, i64, vp, vp]
+    L.osc_rollout_plant_backward_workspace_bytes.argtypes = [vp, vp, i32, szp]
+    L.osc_batch_rollout_plant_backward.argtypes = [
+        vp, vp, i32, ctypes.POINTER(OscRolloutBackwardArgs), scp, sgp, ep, kep,
+        ctypes.POINTER(OscRolloutPlantBackward), vp]
+    for name in PLANT_BACKWARD_SYMBOLS:
         getattr(L, name).restype = ctypes.c_int
     L.osc_batch_solve_backward.argtypes = [vp, i32] + [vp] * 8 + [ctypes.c_size_t, vp]
     L.osc_batch_solve_backward.restype = ctypes.c_int

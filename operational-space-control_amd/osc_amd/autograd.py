@@ -28,6 +28,11 @@ hold qpos / qvel on the device:
     tau, x, status = solve_differentiable_qpos(solver, kin, qpos, qvel, T, mask,
                                                kin_params=KinEnvParams(mass_scale=s))
     loss(tau, x).backward()        # qpos.grad, qvel.grad, s.grad, T.grad: two backward launches
+
+Through the forward dynamics of a plant (include/osc_plant_backward.h):
+
+    qacc = forward_dynamics_differentiable(solver, kin, M, C, J, u, z, qfrc)
+    loss(qacc).backward()          # M.grad, C.grad, J.grad, u.grad, z.grad, qfrc.grad: one launch
 """
 from __future__ import annotations
 
@@ -393,9 +398,9 @@ def rollout_differentiable(solver: OSCBatchSolver, kin: KinematicsBatch, qpos, q
     model's."""
     if plant is not None and getattr(plant, "active", True):
         raise NotImplementedError(
-            "rollout_differentiable: gradients through a plant are out of scope "
-            "(include/osc_plant.h, DESIGN.md §7.5); KinematicsBatch.rollout(..., plant=) runs the "
-            "forward alone")
+            "rollout_differentiable: its backward pass is the matched model's, wrong for a plant "
+            "(include/osc_plant.h, DESIGN.md §7.5); rollout_plant_differentiable differentiates "
+            "through the plant")
     if env_params is not None and not isinstance(env_params, EnvParams):
         raise TypeError("rollout_differentiable: env_params must be an EnvParams")
     if kin_params is not None and not isinstance(kin_params, KinEnvParams):
@@ -450,3 +455,187 @@ def rollout_differentiable(solver: OSCBatchSolver, kin: KinematicsBatch, qpos, q
                                    qpos, qvel, T, sT, refs[0], refs[1], gains, *fields)
     return _Rollout.apply(solver, kin, mask, int(nticks), float(dt), pd, bool(warm), env_params,
                           kin_params, qpos, qvel, T, *fields)
+
+
+class _ForwardDynamics(torch.autograd.Function):
+    """osc_batch_forward_dynamics and its vector-Jacobian product (include/osc_plant_backward.h)."""
+
+    @staticmethod
+    def forward(ctx, solver, kin, M, C, J, u, z, qfrc):
+        nenv = int(M.shape[0])
+        qacc = torch.empty((nenv, kin.nv), dtype=torch.float64, device=kin.device)
+        with torch.cuda.device(kin.device):
+            kin.forward_dynamics_into(solver, qacc, M, C, J, u, z, qfrc)
+        ctx.solver, ctx.kin = solver, kin
+        ctx.save_for_backward(M, J, z, qacc)
+        return qacc
+
+    @staticmethod
+    def backward(ctx, grad_qacc):
+        solver, kin = ctx.solver, ctx.kin
+        M, J, z, qacc = ctx.saved_tensors
+        need = dict(zip(("M", "C", "J", "u", "z", "qfrc"), ctx.needs_input_grad[2:]))
+        if grad_qacc is None or not any(need.values()):
+            return (None,) * 8
+        d = solver.dims
+        nenv, nv, nz = int(M.shape[0]), kin.nv, 3 * d["nc"]
+        if z is None:          # no contact force: J did not enter the forward
+            need["J"] = need["z"] = False
+        opts = dict(dtype=torch.float64, device=kin.device)
+        shape = dict(M=(nenv, nv, nv), C=(nenv, nv), Jc=(nenv, nz, nv), u=(nenv, d["nu"]),
+                     z=(nenv, nz), qfrc=(nenv, nv))
+        need["Jc"] = need.pop("J")
+        out = {k: torch.empty(shape[k], **opts) if need[k] else None for k in shape}
+        if not any(t is not None for t in out.values()):
+            return (None,) * 8
+        g = grad_qacc.to(dtype=torch.float64).contiguous()
+        with torch.cuda.device(kin.device):
+            kin.forward_dynamics_backward(solver, M, J if out["z"] is not None else None, z, qacc,
+                                          g, **{"grad_" + k: t for k, t in out.items()})
+        gJ = None
+        if out["Jc"] is not None:      # the compact contact rows into a J-shaped cotangent
+            r0 = 3 * d["ns"] - nz
+            gJ = torch.zeros((nenv, 6 * d["ns"], nv), **opts)
+            gJ[:, r0:r0 + nz] = out["Jc"]
+        return (None, None, out["M"], out["C"], gJ, out["u"], out["z"], out["qfrc"])
+
+
+def forward_dynamics_differentiable(solver: OSCBatchSolver, kin: KinematicsBatch, M, C, J, u,
+                                    z=None, qfrc_applied=None):
+    """qacc (nenv, nv) = M^-1 (B u + Jc' z + qfrc_applied - C) (KinematicsBatch.
+    forward_dynamics_into: its forward values, bitwise), differentiable with respect to M, C, J, u,
+    z and qfrc_applied -- float64 tensors on kin's device; z / qfrc_applied None = no contact force
+    / no applied force, and J may then be None too.  The backward is one launch
+    (osc_batch_forward_dynamics_backward, include/osc_plant_backward.h) that fills only what
+    autograd asks for.  M's gradient treats all nv^2 entries as independent (-w qacc', not
+    symmetrised); J's is zero outside the contact rows; an env whose M is not positive definite,
+    or with a non-finite input, has a NaN qacc row and zero gradients."""
+    nenv = int(M.shape[0])
+    d = solver.dims
+    u = u if u.stride(-1) == 1 else u.contiguous()
+    if z is not None and z.stride(-1) != 1:
+        z = z.contiguous()
+    if z is None:
+        J = None
+    for name, t, shape in (("M", M, (nenv, kin.nv, kin.nv)), ("C", C, (nenv, kin.nv)),
+                           ("J", J, (nenv, 6 * d["ns"], kin.nv)),
+                           ("qfrc_applied", qfrc_applied, (nenv, kin.nv))):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or
+                              t.device != kin.device or tuple(t.shape) != shape):
+            raise ValueError(f"forward_dynamics_differentiable: {name} must be a float64 tensor of "
+                             f"shape {shape} on {kin.device}")
+    cont = lambda t: None if t is None else t.contiguous()
+    return _ForwardDynamics.apply(solver, kin, cont(M), cont(C), cont(J), u, z,
+                                  cont(qfrc_applied))
+
+
+class _RolloutPlant(torch.autograd.Function):
+    """KinematicsBatch.rollout(..., plant=) with histories and rollout_plant_backward.  As
+    _RolloutSched: qpos, qvel, the held T, schedule.T, the two PD references (held, or the
+    schedule's: seq_refs), the gains and the seven EnvParams and three KinEnvParams fields follow
+    as explicit inputs, then the plant's qfrc_applied and its three KinEnvParams fields (a tensor,
+    or None / a plain value where no gradient is wanted)."""
+
+    NFIXED = 12   # solver .. plant
+
+    @staticmethod
+    def forward(ctx, solver, kin, mask, nticks, dt, warm, env_params, kin_params, sched_mask,
+                seq_refs, pd_mode, plant, qpos, qvel, T, sched_T, pos_ref, quat_ref, gains,
+                *fields):
+        schedule, pd = _RolloutSched._call(sched_mask, seq_refs, pd_mode, T, sched_T, pos_ref,
+                                           quat_ref, gains)
+        if sched_T is None and sched_mask is None and not any(seq_refs):
+            schedule = None
+        res = kin.rollout(solver, qpos, qvel, mask, nticks, dt, T=T, pd=pd, warm=warm,
+                          history=True, env_params=env_params, kin_params=kin_params,
+                          schedule=schedule, plant=plant)
+        ctx.call = (solver, kin, mask, dt, pd, env_params, kin_params, T, schedule, seq_refs)
+        ctx.res = res
+        ctx.mark_non_differentiable(res.status_hist)
+        return res.qpos_hist, res.qvel_hist, res.tau_hist, res.status_hist, res.qacc_hist
+
+    @staticmethod
+    def backward(ctx, gq, gv, gt, _grad_status, ga):
+        solver, kin, mask, dt, pd, env_params, kin_params, T, schedule, seq_refs = ctx.call
+        names = ("qpos0", "qvel0", "T", "T_seq", "pos_ref_seq" if seq_refs[0] else "pos_ref",
+                 "quat_ref_seq" if seq_refs[1] else "quat_ref", "gains") + \
+            tuple("env." + k for k in EnvParams.FIELDS) + \
+            tuple("kin." + k for k in KinEnvParams.FIELDS) + ("plant.qfrc_applied",) + \
+            tuple("plant.kin." + k for k in KinEnvParams.FIELDS)
+        need = ctx.needs_input_grad[_RolloutPlant.NFIXED:]
+        want = tuple(n for n, w in zip(names, need) if w)
+        none = (None,) * (_RolloutPlant.NFIXED + len(names))
+        if not want or all(g is None for g in (gq, gv, gt, ga)):
+            return none
+        cot = [None if g is None else g.to(dtype=torch.float64).contiguous()
+               for g in (gq, gv, gt, ga)]
+        g = kin.rollout_plant_backward(solver, ctx.res, mask, dt, T=T, pd=pd,
+                                       grad_qpos_hist=cot[0], grad_qvel_hist=cot[1],
+                                       grad_tau_hist=cot[2], grad_qacc_hist=cot[3],
+                                       env_params=env_params, kin_params=kin_params, want=want,
+                                       schedule=schedule)
+        return none[:_RolloutPlant.NFIXED] + tuple(g.get(n) for n in names)
+
+
+def rollout_plant_differentiable(solver: OSCBatchSolver, kin: KinematicsBatch, qpos, qvel, mask,
+                                 nticks: int, dt: float, T=None, pd=None, warm: bool = True,
+                                 env_params=None, kin_params=None, schedule=None, plant=None):
+    """(qpos_hist, qvel_hist, tau_hist, status_hist, qacc_hist) of the closed-loop rollout against
+    a plant (KinematicsBatch.rollout(..., history=True, plant=plant): its forward values, bitwise;
+    plant a kinematics.Plant with a field set).  It carries everything rollout_differentiable
+    carries -- gradients to qpos, qvel, a held T, the tensor fields of env_params and kin_params
+    (the CONTROLLER's), schedule.T, schedule.pos_ref / quat_ref or the held PD references, and the
+    gains when they are a float64 tensor of 4 -- and, through the plant, gradients to
+    plant.qfrc_applied (held or per tick: the gradient has its shape) and the tensor fields of
+    plant.kin_params.  Only float64 tensors on kin's device that require a gradient get one.  The
+    backward is one call (osc_batch_rollout_plant_backward, include/osc_plant_backward.h) that
+    fills only what autograd asks for; a loss may touch any slab of the four histories."""
+    from .kinematics import Plant, RolloutSchedule
+    if not isinstance(plant, Plant) or not plant.active:
+        raise ValueError("rollout_plant_differentiable: plant must be a Plant with a field set "
+                         "(rollout_differentiable is the call without one)")
+    if env_params is not None and not isinstance(env_params, EnvParams):
+        raise TypeError("rollout_plant_differentiable: env_params must be an EnvParams")
+    for block in (kin_params, plant.kin_params):
+        if block is not None and not isinstance(block, KinEnvParams):
+            raise TypeError("rollout_plant_differentiable: kin_params must be a KinEnvParams")
+    if T is not None and pd is not None:
+        raise ValueError("rollout_plant_differentiable: at most one of T and pd may be given")
+    if T is None and pd is None and (schedule is None or schedule.T is None):
+        raise ValueError("rollout_plant_differentiable: one of T, pd and schedule.T must be given")
+    grad_t = lambda r: isinstance(r, torch.Tensor) and r.requires_grad
+    d = solver.dims
+    nenv = int(qpos.shape[0])
+    qpos = kin._dev(qpos, (nenv, kin.nq), "qpos")
+    qvel = kin._dev(qvel, (nenv, kin.nv), "qvel")
+    if T is not None:
+        T = kin._dev(T, (nenv, d["ns"], 6), "T")
+    sc = schedule if schedule is not None else RolloutSchedule()
+    pos_ref, quat_ref, gains = pd if pd is not None else (None, None, None)
+    seq_refs = (sc.pos_ref is not None, sc.quat_ref is not None)
+    refs = [sc.pos_ref if seq_refs[0] else pos_ref, sc.quat_ref if seq_refs[1] else quat_ref]
+    for r in refs + [sc.T]:
+        if grad_t(r) and (r.dtype != torch.float64 or r.device != kin.device):
+            raise ValueError("rollout_plant_differentiable: a schedule member or PD reference "
+                             f"that requires a gradient must be float64 on {kin.device}")
+    if grad_t(gains) and (gains.dtype != torch.float64 or gains.device != kin.device or
+                          tuple(gains.shape) != (4,)):
+        raise ValueError("rollout_plant_differentiable: gains that require a gradient must be a "
+                         f"float64 tensor of 4 on {kin.device}")
+    fields = []
+    for block, cls, label in ((env_params, EnvParams, "EnvParams"),
+                              (kin_params, KinEnvParams, "KinEnvParams"),
+                              (plant, ("qfrc_applied",), "Plant"),
+                              (plant.kin_params, KinEnvParams, "Plant.kin_params")):
+        for name in (cls if isinstance(cls, tuple) else cls.FIELDS):
+            a = getattr(block, name) if block is not None else None
+            if grad_t(a):
+                if a.device != kin.device or a.dtype != torch.float64:
+                    raise ValueError(f"rollout_plant_differentiable: {label}.{name} requires a "
+                                     f"gradient and must be float64 on {kin.device}")
+                fields.append(a)
+            else:
+                fields.append(None)
+    return _RolloutPlant.apply(solver, kin, mask, int(nticks), float(dt), bool(warm), env_params,
+                               kin_params, sc.mask, seq_refs, pd is not None, plant, qpos, qvel,
+                               T, sc.T, refs[0], refs[1], gains, *fields)

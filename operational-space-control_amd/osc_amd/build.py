@@ -30,7 +30,8 @@ SOURCES = ["osc_ipm_go2.hip", "osc_ipm_walter.hip", "osc_ipm_wheels.hip", "osc_m
            "osc_setup.hip", "osc_gi.hip", "osc_dual.hip", "osc_kinematics.hip",
            "osc_producers.hip", "osc_rollout.hip", "osc_backward.hip", "osc_backward_data.hip",
            "osc_backward_env.hip", "osc_kin_backward.hip", "osc_rollout_backward.hip",
-           "osc_rollout_schedule.hip", "osc_forward_dynamics.hip", "osc_api.hip",
+           "osc_rollout_schedule.hip", "osc_forward_dynamics.hip",
+           "osc_forward_dynamics_backward.hip", "osc_api.hip",
            "osc_model.cpp", "osc_mjcf.cpp", "osc_host_feed.cpp"]
 # every header of csrc/ (the up-to-date check's dependency list: a new header is picked up by name)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp"))
@@ -74,7 +75,8 @@ def build(verbose: bool = False, force: bool = False, out: str | None = None,
                                                      "osc_kin_backward.h",
                                                      "osc_rollout_backward.h",
                                                      "osc_rollout_schedule.h",
-                                                     "osc_plant.h")] + [__file__]
+                                                     "osc_plant.h",
+                                                     "osc_plant_backward.h")] + [__file__]
     variant = out != OUT
     if not force and os.path.exists(out):
         t_out = os.path.getmtime(out)

@@ -14,6 +14,9 @@ controller's model, not a simulator), KinematicsBatch.integrate_into(...) is its
 include/osc_plant.h: KinematicsBatch.forward_dynamics(...) is qacc = M^-1 (B u + Jc' z + qfrc - C),
 and rollout(..., plant=Plant(...)) integrates that of a plant with its own mass / COM / armature
 and applied forces instead of the QP's dv (still no ground).
+include/osc_plant_backward.h: KinematicsBatch.forward_dynamics_backward(...) is the forward
+dynamics' vector-Jacobian product and rollout_plant_backward(...) the plant rollout's backward
+(autograd.forward_dynamics_differentiable and rollout_plant_differentiable wrap the pairs).
 The kinematic tree comes from operational-space-control_amd/config/<robot>_kinematics.json
 (illustrative trees: the reference's MJCF files are not vendored) or from any osc_kin_desc.
 Launches go through the C-ABI on the current torch stream; there is no CPU fallback.
@@ -477,6 +480,66 @@ class KinematicsBatch:
         with torch.cuda.device(self.device):
             return self.forward_dynamics_into(solver, qacc, k.M, k.C, k.J, tau, z, f)
 
+    def forward_dynamics_backward(self, solver, M, J, z, qacc, grad_qacc, grad_M=None,
+                                  grad_C=None, grad_Jc=None, grad_u=None, grad_z=None,
+                                  grad_qfrc=None, stream=None):
+        """osc_batch_forward_dynamics_backward (include/osc_plant_backward.h), launch only: with
+        w = M^-1 grad_qacc, into the outputs that are given (None = not computed; at least one)
+            grad_M (nenv, nv, nv) = -w qacc' (not symmetrised), grad_C (nenv, nv) = -w,
+            grad_Jc (nenv, 3 nc, nv) = z w' (the contact rows only), grad_qfrc (nenv, nv) = w,
+            grad_u (nenv, nu) = w[nv - nu:], grad_z (nenv, 3 nc) = Jc w.
+        M, J and z are what forward_dynamics_into took (z None: J, grad_Jc and grad_z must be None
+        too; J may be None unless grad_z is wanted) and qacc what it returned.  z, grad_qacc,
+        grad_u and grad_z may be strided views with contiguous rows; everything else is
+        contiguous.  An env the forward gave a NaN row, or with a non-finite entry in what is
+        read here, gets zeros in every output.  Returns the dict of the outputs given."""
+        d = solver.dims
+        nenv, nv, nz = int(qacc.shape[0]), self.nv, 3 * d["nc"]
+        dense = dict(M=(M, (nenv, nv, nv)), J=(J, (nenv, 6 * self.ns, nv)),
+                     qacc=(qacc, (nenv, nv)), grad_M=(grad_M, (nenv, nv, nv)),
+                     grad_C=(grad_C, (nenv, nv)), grad_Jc=(grad_Jc, (nenv, nz, nv)),
+                     grad_qfrc=(grad_qfrc, (nenv, nv)))
+        rows = dict(z=(z, nz), grad_qacc=(grad_qacc, nv), grad_u=(grad_u, d["nu"]),
+                    grad_z=(grad_z, nz))
+        if z is None and (J is not None or grad_Jc is not None or grad_z is not None):
+            raise ValueError("z is None: J, grad_Jc and grad_z must be None as well")
+        if grad_z is not None and J is None:
+            raise ValueError("J: required for grad_z")
+        outs = dict(M=grad_M, C=grad_C, Jc=grad_Jc, u=grad_u, z=grad_z, qfrc=grad_qfrc)
+        if all(t is None for t in outs.values()):
+            raise ValueError("forward_dynamics_backward: at least one output is required")
+        for name, (t, shape) in dense.items():
+            if t is None:
+                if name in ("M", "qacc"):
+                    raise ValueError(f"{name}: required")
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or \
+                    t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"{name}: expected a contiguous float64 tensor of shape {shape} "
+                                 f"on {self.device}")
+        stride = {}
+        for name, (t, w) in rows.items():
+            if t is None:
+                if name == "grad_qacc":
+                    raise ValueError("grad_qacc: required")
+                stride[name] = 0
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or \
+                    t.device != self.device or tuple(t.shape) != (nenv, w) or \
+                    (w > 1 and t.stride(1) != 1) or (nenv > 1 and t.stride(0) < w):
+                raise ValueError(f"{name}: expected (nenv, {w}) float64 with contiguous rows on "
+                                 f"{self.device}")
+            stride[name] = t.stride(0) if nenv > 1 else w
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = _lib.lib().osc_batch_forward_dynamics_backward(
+            solver._h, nenv, ptr(M), ptr(J), ptr(z), stride["z"], ptr(qacc), ptr(grad_qacc),
+            stride["grad_qacc"], ptr(grad_M), ptr(grad_C), ptr(grad_Jc), ptr(grad_u),
+            stride["grad_u"], ptr(grad_z), stride["grad_z"], ptr(grad_qfrc),
+            ctypes.c_void_p(self._stream(stream, self.device)))
+        if rc != 0:
+            raise _lib.OSCError("osc_batch_forward_dynamics_backward", rc)
+        return {k: t for k, t in outs.items() if t is not None}
+
     def _plant_block(self, plant, res, nenv, nticks, history):
         """(osc_rollout_plant struct, what it points to) of a rollout with plant=; with history the
         result's qacc_hist is allocated when the plant has a field.  Shape errors raise here."""
@@ -753,12 +816,50 @@ class KinematicsBatch:
         gains' come back summed over the envs ((3,), (4,), (nticks, 3), ...), a per-env
         reference's per env.  dt and the mask get no gradient.
         Returns a dict name -> tensor."""
-        from .solver import EnvGrads
         if getattr(result, "plant", None) is not None:
             raise NotImplementedError(
-                "rollout_backward: the result came from a rollout against a plant; gradients "
-                "through the plant are out of scope (include/osc_plant.h, DESIGN.md §7.5) and "
-                "the matched model's would be wrong for it")
+                "rollout_backward: the result came from a rollout against a plant, and the "
+                "matched model's gradients would be wrong for it (include/osc_plant.h, DESIGN.md "
+                "§7.5); rollout_plant_backward differentiates through the plant")
+        return self._rollout_backward(solver, result, mask, dt, T, pd, grad_qpos_hist,
+                                      grad_qvel_hist, grad_tau_hist, env_params, kin_params, want,
+                                      stream, workspace, schedule, False, None)
+
+    def rollout_plant_backward_workspace_bytes(self, solver, nenv: int) -> int:
+        nb = ctypes.c_size_t()
+        rc = _lib.lib().osc_rollout_plant_backward_workspace_bytes(solver._h, self._h, nenv,
+                                                                   ctypes.byref(nb))
+        if rc != 0:
+            raise _lib.OSCError("osc_rollout_plant_backward_workspace_bytes", rc)
+        return nb.value
+
+    PLANT_GRADS = ("plant.qfrc_applied",) + tuple("plant.kin." + k for k in KinEnvParams.FIELDS)
+
+    def rollout_plant_backward(self, solver, result, mask, dt, T=None, pd=None,
+                               grad_qpos_hist=None, grad_qvel_hist=None, grad_tau_hist=None,
+                               grad_qacc_hist=None, env_params=None, kin_params=None,
+                               want=("qpos0", "qvel0"), stream=None, workspace="alloc",
+                               schedule=None) -> dict:
+        """osc_batch_rollout_plant_backward (include/osc_plant_backward.h): rollout_backward
+        through the plant of rollout(..., history=True, plant=...), which is taken from
+        result.plant.  One more cotangent, grad_qacc_hist (nticks, nenv, nv), and in `want`, next
+        to rollout_backward's names, PLANT_GRADS: "plant.qfrc_applied" -- (nenv, nv), the sum over
+        the ticks, for a held force (or none: the gradient at zero), (nticks, nenv, nv) for a
+        per-tick one -- and "plant.kin.<field>" of the plant's KinEnvParams (it must have one).
+        kin_params / "kin.<field>" stay the CONTROLLER's.  A result without a plant is
+        rollout_backward, bitwise.  Returns a dict name -> tensor."""
+        return self._rollout_backward(solver, result, mask, dt, T, pd, grad_qpos_hist,
+                                      grad_qvel_hist, grad_tau_hist, env_params, kin_params, want,
+                                      stream, workspace, schedule, True, grad_qacc_hist)
+
+    def _rollout_backward(self, solver, result, mask, dt, T, pd, grad_qpos_hist, grad_qvel_hist,
+                          grad_tau_hist, env_params, kin_params, want, stream, workspace,
+                          schedule, plant_call, grad_qacc_hist) -> dict:
+        """rollout_backward and rollout_plant_backward (plant_call: the entry that takes a plant,
+        whose block is NULL when the result has none)."""
+        from .solver import EnvGrads
+        me = "rollout_plant_backward" if plant_call else "rollout_backward"
+        plant = getattr(result, "plant", None) if plant_call else None
         want = tuple(want)
         sched_call = schedule is not None or any(w in self.ROLLOUT_SCHEDULE_GRADS for w in want)
         if T is not None and pd is not None:
@@ -766,14 +867,15 @@ class KinematicsBatch:
         if T is None and pd is None and (schedule is None or schedule.T is None):
             raise ValueError("one of T, pd and schedule.T must be given")
         if result.qpos_hist is None or result.qvel_hist is None or result.status_hist is None:
-            raise ValueError("rollout_backward: the forward call needs history=True")
+            raise ValueError(f"{me}: the forward call needs history=True")
         for w in want:
-            if w not in self.ROLLOUT_GRADS + self.ROLLOUT_SCHEDULE_GRADS:
-                raise ValueError(f"rollout_backward: unknown gradient {w!r}")
+            if w not in self.ROLLOUT_GRADS + self.ROLLOUT_SCHEDULE_GRADS + \
+                    (self.PLANT_GRADS if plant is not None else ()):
+                raise ValueError(f"{me}: unknown gradient {w!r}")
         if not want:
-            raise ValueError("rollout_backward: nothing asked for")
+            raise ValueError(f"{me}: nothing asked for")
         if pd is not None and "T" in want:
-            raise ValueError("rollout_backward: no grad_T with PD targets")
+            raise ValueError(f"{me}: no grad_T with PD targets")
         d = solver.dims
         nticks, nenv = int(result.status_hist.shape[0]), int(result.qpos_hist.shape[1])
         o = dict(device=self.device, dtype=torch.float64)
@@ -824,40 +926,76 @@ class KinematicsBatch:
             a.kin_grads = ctypes.pointer(ckg)
             keep.append(ckg)
             out.update({"kin." + k: getattr(kg, k) for k in kfields})
+        pl = None
+        if plant is not None:     # the forward's plant block, the cotangent, the plant's gradients
+            pl = _lib.OscRolloutPlantBackward()
+            if plant.kin_params is not None:
+                kc, kk = self._kin_block(plant.kin_params, nenv)
+                keep += [kc] + kk
+                pl.kin_params = ctypes.pointer(kc)
+            seq = False
+            if plant.qfrc_applied is not None:
+                f = plant.qfrc_applied
+                f = f if isinstance(f, torch.Tensor) else np.asarray(f, dtype=np.float64)
+                seq = f.ndim == 3
+                f = self._dev(f, (nticks, nenv, self.nv) if seq else (nenv, self.nv),
+                              "plant.qfrc_applied")
+                setattr(pl, "qfrc_applied_seq" if seq else "qfrc_applied", f.data_ptr())
+                keep.append(f)
+            gah = self._grad_tensor(grad_qacc_hist, (nticks, nenv, self.nv), "grad_qacc_hist")
+            pl.grad_qacc_hist = ptr(gah)
+            keep.append(gah)
+            if "plant.qfrc_applied" in want:
+                g = torch.empty((nticks, nenv, self.nv) if seq else (nenv, self.nv), **o)
+                setattr(pl, "grad_qfrc_applied_seq" if seq else "grad_qfrc_applied", g.data_ptr())
+                out["plant.qfrc_applied"] = g
+            pfields = [w[10:] for w in want if w.startswith("plant.kin.")]
+            if pfields:
+                if plant.kin_params is None:
+                    raise ValueError("rollout_plant_backward: plant.kin.<field> needs a plant "
+                                     "with kin_params")
+                pg = KinEnvGrads.empty(nenv, self.nbody, self.nv, self.device, pfields)
+                cpg = _lib.OscKinEnvGrads(**{k: getattr(pg, k).data_ptr() for k in pfields})
+                pl.kin_grads = ctypes.pointer(cpg)
+                keep.append(cpg)
+                out.update({"plant.kin." + k: getattr(pg, k) for k in pfields})
+        elif grad_qacc_hist is not None:
+            raise ValueError(f"{me}: grad_qacc_hist, but the result has no plant and no qacc_hist")
         if isinstance(workspace, str):
-            workspace = torch.empty((max(self.rollout_backward_workspace_bytes(solver, nenv) // 8,
-                                         2),), **o)
+            nbytes = self.rollout_plant_backward_workspace_bytes(solver, nenv) if pl is not None \
+                else self.rollout_backward_workspace_bytes(solver, nenv)
+            workspace = torch.empty((max(nbytes // 8, 2),), **o)
         if workspace is not None:
             a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
         s = ctypes.c_void_p(self._stream(stream, self.device))
-        if sched_call:
-            # the library's outputs are per env; a shared reference's and the gains' are summed here
+        raw, sg = {}, None
+        if sched_call:   # the library's outputs are per env
             sshape = dict(T_seq=(nticks, nenv, d["ns"], 6), pos_ref=(nenv, 3), quat_ref=(nenv, 4),
                           pos_ref_seq=(nticks, nenv, 3), quat_ref_seq=(nticks, nenv, 4),
                           gains=(nenv, 4))
             raw = {w: torch.empty(sshape[w], **o) for w in want if w in sshape}
             sg = _lib.OscRolloutScheduleGrads(**{"grad_" + w: t.data_ptr() for w, t in raw.items()})
-            with torch.cuda.device(self.device):
-                rc = _lib.lib().osc_batch_rollout_backward_sched(
-                    solver._h, self._h, nenv, ctypes.byref(a),
-                    ctypes.byref(sc) if sc is not None else None, ctypes.byref(sg), ep, kp, s)
-            if rc != 0:
-                raise _lib.OSCError("osc_batch_rollout_backward_sched", rc)
-            for w, t in raw.items():
-                if w == "gains":
-                    t = t.sum(0)
-                elif w in ("pos_ref", "quat_ref") and not getattr(a, w + "_per_env"):
-                    t = t.sum(0)
-                elif w in ("pos_ref_seq", "quat_ref_seq") and not per_env_seq[w[:-4]]:
-                    t = t.sum(1)
-                out[w] = t
-            keep += [sg] + list(raw.values())
+        ref = lambda c: ctypes.byref(c) if c is not None else None
+        head = (solver._h, self._h, nenv, ctypes.byref(a))
+        if plant_call:
+            entry, tail = "osc_batch_rollout_plant_backward", (ref(sc), ref(sg), ep, kp, ref(pl), s)
+        elif sched_call:
+            entry, tail = "osc_batch_rollout_backward_sched", (ref(sc), ref(sg), ep, kp, s)
         else:
-            with torch.cuda.device(self.device):
-                rc = _lib.lib().osc_batch_rollout_backward(solver._h, self._h, nenv,
-                                                           ctypes.byref(a), ep, kp, s)
-            if rc != 0:
-                raise _lib.OSCError("osc_batch_rollout_backward", rc)
+            entry, tail = "osc_batch_rollout_backward", (ep, kp, s)
+        with torch.cuda.device(self.device):
+            rc = getattr(_lib.lib(), entry)(*head, *tail)
+        if rc != 0:
+            raise _lib.OSCError(entry, rc)
+        for w, t in raw.items():     # a shared reference's and the gains': summed over the envs
+            if w == "gains":
+                t = t.sum(0)
+            elif w in ("pos_ref", "quat_ref") and not getattr(a, w + "_per_env"):
+                t = t.sum(0)
+            elif w in ("pos_ref_seq", "quat_ref_seq") and not per_env_seq[w[:-4]]:
+                t = t.sum(1)
+            out[w] = t
+        keep += [sg, pl] + list(raw.values())
         out._keep = keep + [workspace, hq, hv, hs, gqh, gvh, gth]   # alive until the stream is done
         return out
 
