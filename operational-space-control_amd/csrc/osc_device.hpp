@@ -409,15 +409,23 @@ __device__ __forceinline__ double keep_m(unsigned long long m, double v) {
 // interior point's situation at 4,096 envs.  Volatile: the triangular solves place them between
 // the DPP FMAs on purpose -- their three VALU instructions are the two wait states the next DPP
 // read of a just-written value needs, so those FMAs carry no s_nop of their own.
-// sel_eq: `set` on the lane l == K of each row, `clear` elsewhere.
-// (the compare is an asm statement of its own: hipcc pads any inline asm that reads a register
-// the previous inline asm wrote with an s_nop -- gfx950's conservative forwarding-hazard rule for
-// asm producers -- so the compare, which reads only l, goes between the DPP FMA that wrote `set`
-// and the selects that read it)
-template <int K>
+// A VALU-written mask must be 2 wait states old when a select reads it (gfx950; the compiler pads
+// this pair in its own code and not in asm: tools/check_dpp_hazards.py RULES).  So
+// the compare is an asm statement of its own, issued well ahead of its selects: volatile asm
+// statements keep their order, and the callers put at least one other volatile statement of two
+// wait states or more (the previous step's selects, a guarded broadcast) between the compare and
+// the mask's first select.  PAD: for a compare with nothing to put there (a solve's first step),
+// the wait states ride inside its string.  tests/test_asm_hazards.py scans every unit for a pair
+// left short.
+// lane_eq: the lane l == K of each row; lane_gt: the lanes l > K.
+template <int K, int PAD = 0>
 __device__ __forceinline__ unsigned long long lane_eq(int l) {
   unsigned long long m;
-  asm volatile("v_cmp_eq_u32_e64 %0, %1, %2" : "=s"(m) : "n"(K), "v"(l));
+  if constexpr (PAD > 0)
+    asm volatile("v_cmp_eq_u32_e64 %0, %1, %2\n\ts_nop %3"
+                 : "=s"(m) : "n"(K), "v"(l), "n"(PAD - 1));
+  else
+    asm volatile("v_cmp_eq_u32_e64 %0, %1, %2" : "=s"(m) : "n"(K), "v"(l));
   return m;
 }
 template <int K>
@@ -426,6 +434,7 @@ __device__ __forceinline__ unsigned long long lane_gt(int l) {
   asm volatile("v_cmp_lt_u32_e64 %0, %1, %2" : "=s"(m) : "n"(K), "v"(l));
   return m;
 }
+// `set` on the lanes of m, `clear` elsewhere
 __device__ __forceinline__ double sel_mask(unsigned long long m, double set, double clear) {
   int lo, hi;
   asm volatile("v_cndmask_b32_e64 %0, %2, %3, %6\n\t"
@@ -435,14 +444,9 @@ __device__ __forceinline__ double sel_mask(unsigned long long m, double set, dou
                  "v"(__double2hiint(set)), "s"(m));
   return __hiloint2double(hi, lo);
 }
-template <int K>
-__device__ __forceinline__ double sel_eq(int l, double set, double clear) {
-  return sel_mask(lane_eq<K>(l), set, clear);
-}
-// keep_gt: v on the lanes l > K of each row, +0.0 elsewhere.
-template <int K>
-__device__ __forceinline__ double keep_gt(int l, double v) {
-  const unsigned long long m = lane_gt<K>(l);
+// v on the lanes of m, +0.0 elsewhere (keep_m, volatile: stays behind the statements between the
+// compare and it)
+__device__ __forceinline__ double keep_mask(unsigned long long m, double v) {
   int lo, hi;
   asm volatile("v_cndmask_b32_e64 %0, 0, %2, %4\n\t"
                "v_cndmask_b32_e64 %1, 0, %3, %4"

@@ -90,17 +90,24 @@ __device__ __forceinline__ void ldl_rows(double (&c0)[N], double (&c1)[N], doubl
   auto prep = [&](auto kc, double& t0, double& t1) {
     constexpr int k = decltype(kc)::value;
     constexpr int s = k / kRow, kl = k % kRow;
+    // the lanes l > k, compared ahead of the guarded broadcast: its three wait states lie between
+    // the mask's write and the selects below (osc_device.hpp lane_gt)
+    const unsigned long long gt = lane_gt<kl>(l);
     const double own = (s == 0) ? c0[k] + du : c1[k];
     const double dk = bcast_guarded<kl>(own > ((s == 0) ? thr0 : thr1) ? own : 1e128);
     const double inv = recip1(dk);
     sdinv[k] = inv;
     c0[k] = -c0[k] * inv;
     c1[k] = -c1[k] * inv;
-    // (lanes l > k by a compare on the lane index, osc_device.hpp keep_gt; in slot 1 the mirror
-    // lanes past N keep their multipliers too and so stay exact copies of column N - 1)
-    t0 = keep_gt<k>(l, c0[k]);
-    if constexpr (k < kRow) t1 = c1[k];
-    else t1 = keep_gt<k - kRow>(l, c1[k]);
+    // (in slot 1 the mirror lanes past N keep their multipliers too and so stay exact copies of
+    // column N - 1)
+    if constexpr (k < kRow) {
+      t0 = keep_mask(gt, c0[k]);
+      t1 = c1[k];
+    } else {
+      t0 = 0.0;   // (no lane of slot 0 lies past pivot k >= 16; not read: upd)
+      t1 = keep_mask(gt, c1[k]);
+    }
   };
   // one trailing FMA pair of step k, row i (NOP: the DPP source was written just before)
   auto upd = [&](auto kc, auto ic, double t0, double t1) {
@@ -172,19 +179,25 @@ __device__ __forceinline__ void ldl_fwd_rows(const double (&c0)[N], const double
     a1 = z1;
     return;
   }
+  // step k + 1's lane mask is compared ahead of step k's selects, which with step k's FMAs are
+  // its wait states (osc_device.hpp lane_eq); the selects are the DPP read's wait states
+  unsigned long long m = lane_eq<0, 1>(l);
   static_for<0, N>([&](auto kc) {
     constexpr int k = decltype(kc)::value;
     constexpr int s = k / kRow, kl = k % kRow;
+    unsigned long long mn = m;
+    if constexpr (k + 1 < N) mn = lane_eq<(k + 1) % kRow>(l);
     if constexpr (s == 0) {
-      z0 = sel_eq<kl>(l, a0, z0);   // (its three VALU instructions: the DPP read's wait states)
+      z0 = sel_mask(m, a0, z0);
       const double p = a0;
       fmac_bcast<kl>(a1, p, c1[k]);
       if constexpr (k < kRow - 1) fmac_bcast<kl>(a0, p, c0[k]);
     } else {
-      z1 = sel_eq<kl>(l, a1, z1);
+      z1 = sel_mask(m, a1, z1);
       const double p = a1;
       fmac_bcast<kl>(a1, p, c1[k]);
     }
+    m = mn;
   });
   a0 = z0;
   a1 = z1;
@@ -200,19 +213,23 @@ __device__ __forceinline__ void ldl_bwd_rows(const double (&c0)[N], const double
     a1 = x1 * dinv1;
     return;
   }
+  unsigned long long m = lane_eq<(N - 1) % kRow, 1>(l);   // masks a step ahead, as in ldl_fwd_rows
   static_for<0, N>([&](auto kc) {
     constexpr int k = N - 1 - decltype(kc)::value;
     constexpr int s = k / kRow, kl = k % kRow;
+    unsigned long long mn = m;
+    if constexpr (k >= 1) mn = lane_eq<(k - 1) % kRow>(l);
     if constexpr (s == 0) {
-      x0 = sel_eq<kl>(l, a0, x0);
+      x0 = sel_mask(m, a0, x0);
       const double p = a0;
       if constexpr (k >= 1) fmac_bcast<kl>(a0, p, c0[k]);
     } else {
-      x1 = sel_eq<kl>(l, a1, x1);
+      x1 = sel_mask(m, a1, x1);
       const double p = a1;
       fmac_bcast<kl>(a0, p, c0[k]);
       if constexpr (k > kRow) fmac_bcast<kl>(a1, p, c1[k]);
     }
+    m = mn;
   });
   a0 = x0 * dinv0;
   a1 = x1 * dinv1;

@@ -6,13 +6,28 @@ every instruction it issues, s_nop included (tools/mb/mb_issue.hip), and hipcc p
 between two dependent inline-asm statements with an s_nop (its conservative forwarding-hazard rule
 for asm producers on gfx950).  The per-step asm statements of ldl_fwd_rows / ldl_bwd_rows /
 dot_rows (osc_ipm_ldl.hpp) cost an s_nop per step that way; one statement per solve, scheduled by
-hand, needs none: each step's lane-mask compare is issued one step early (the mask's one wait
-state) and each DPP read of a value written by the previous step's FMA sits two instructions
-after it (the selects are the wait states).  Same instructions on the same values in the same
-order per accumulator as the C++ forms: bitwise the same results.
+hand, needs none: each step's lane-mask compare is issued a whole step early, into the mask
+register the current step does not select on (VCC and one SGPR pair take turns), so the current
+step's selects and FMAs are the mask's wait states, and each DPP read of a value written by the
+previous step's FMA sits behind the compare and the selects.  Same instructions on the same values
+in the same order per accumulator as the C++ forms: bitwise the same results.
+
+Every statement is emitted through Sched, which takes its wait states from the rule table of
+tools/check_dpp_hazards.py (pinned to the compiler by tests/test_hazard_rules.py) and pads with an
+s_nop whatever an arrangement leaves short; values written before the statement count as written
+by the instruction just ahead of it.
 
     python tools/gen_ipm_asm.py        (rewrites the header)"""
 import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from check_dpp_hazards import rule  # noqa: E402
+
+DPP_WAITS = rule("dpp_src").waits            # VALU write of a VGPR -> DPP read of it
+TRANS_WAITS = rule("valu_vgpr", "trans_vgpr").waits   # transcendental result -> VALU read
+VCC_WAITS = rule("valu_vcc").waits           # VALU write of VCC -> VALU read of it as a mask
+SGPR_WAITS = rule("valu_sgpr").waits         # the same through an SGPR pair
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(REPO, "operational-space-control_amd", "csrc", "osc_ipm_asm.hpp")
@@ -21,82 +36,97 @@ DPP = " row_mask:0xf bank_mask:0xf"
 
 
 def fmac(dst, src, m, k):
-    return f"v_fmac_f64_dpp {reg(dst)}, {reg(src)}, %[{m}] row_newbcast:{k}{DPP}"
+    return Ins(f"v_fmac_f64_dpp {reg(dst)}, {reg(src)}, %[{m}] row_newbcast:{k}{DPP}",
+               w=[dst], r=[dst, m], dpp=[src])
 
 
 # a0, a1, z0, z1 live in fixed VGPR pairs (register constraints): the selects need their halves,
 # which an operand of the asm cannot name
 PIN = {"a0": 0, "a1": 2, "z0": 4, "z1": 6}
+# the two lane masks that take turns: VCC and an SGPR pair the compiler picks
+MASKS = ("vcc", "%[m]")
 
 
 def reg(name):
     return f"v[{PIN[name]}:{PIN[name] + 1}]" if name in PIN else f"%[{name}]"
 
 
-def sel(dst, set_):
-    # dst = vcc ? set : dst, 64-bit as two halves
+def sel(dst, set_, mask):
+    # dst = mask ? set : dst, 64-bit as two halves
     d, s_ = PIN[dst], PIN[set_]
-    return [f"v_cndmask_b32 v{d}, v{d}, v{s_}, vcc",
-            f"v_cndmask_b32 v{d + 1}, v{d + 1}, v{s_ + 1}, vcc"]
+    e64 = "" if mask == "vcc" else "_e64"
+    return [Ins(f"v_cndmask_b32{e64} v{d + h}, v{d + h}, v{s_ + h}, {mask}", w=[dst],
+                r=[dst, set_], rmask=[mask]) for h in (0, 1)]
 
 
-def cmp(k):
-    return f"v_cmp_eq_u32 vcc, {k}, %[l]"
+def cmp(k, mask):
+    e64 = "" if mask == "vcc" else "_e64"
+    return Ins(f"v_cmp_eq_u32{e64} {mask}, {k}, %[l]", r=["l"], wmask=[mask])
+
+
+def solve(steps, hoist=None):
+    """steps: (lane, selects' (dst, set), FMAs) in order.  Step i selects on MASKS[i % 2]; the
+    compare for step i + 1 opens step i, so a whole step lies between a mask and its selects.
+    hoist: step 0's first FMA, which touches neither register of the selects, goes ahead of them
+    as the first mask's second wait state (tried both ways; the fewer wait slots win)"""
+    if hoist is None:
+        return min((solve(steps, h) for h in (True, False)),
+                   key=lambda out: sum(t.startswith("s_nop") for t in out))
+    sc = Sched()
+    sc.emit(cmp(steps[0][0], MASKS[0]))
+    for i, (_, (dst, set_), fmas) in enumerate(steps):
+        if i + 1 < len(steps):
+            sc.emit(cmp(steps[i + 1][0], MASKS[(i + 1) % 2]))
+        sels = sel(dst, set_, MASKS[i % 2])
+        if hoist and i == 0 and fmas and not fmas[0].w & {dst, set_}:
+            body = fmas[:1] + sels + fmas[1:]
+        else:
+            body = sels + fmas
+        for ins in body:
+            sc.emit(ins)
+    return sc.out
 
 
 def fwd(n):
-    ins = ["s_nop 1", cmp(0)]
+    steps = []
     for k in range(n):
         kl = k % ROW
-        last = k == n - 1
         if k < ROW:
-            ins += sel("z0", "a0")
-            if k < ROW - 1:
-                ins.append(fmac("a1", "a0", f"c1_{k}", kl))
-                ins.append(cmp((k + 1) % ROW))
-                ins.append(fmac("a0", "a0", f"c0_{k}", kl))
-            else:   # k = 15: no slot-0 update; the compare goes before the FMA (its wait state)
-                ins.append(cmp((k + 1) % ROW))
-                ins.append(fmac("a1", "a0", f"c1_{k}", kl))
+            fmas = [fmac("a1", "a0", f"c1_{k}", kl)]
+            if k < ROW - 1:   # k = 15: no slot-0 update
+                fmas.append(fmac("a0", "a0", f"c0_{k}", kl))
+            steps.append((kl, ("z0", "a0"), fmas))
         else:
-            ins += sel("z1", "a1")
-            if not last:
-                ins.append(cmp((k + 1) % ROW))
-            ins.append(fmac("a1", "a1", f"c1_{k}", kl))
+            steps.append((kl, ("z1", "a1"), [fmac("a1", "a1", f"c1_{k}", kl)]))
     uses = [f"c0_{k}" for k in range(ROW - 1)] + [f"c1_{k}" for k in range(n)]
-    return ins, uses
+    return solve(steps), uses
 
 
 def bwd(n):
-    ins = ["s_nop 1", cmp((n - 1) % ROW)]
+    steps = []
     for k in range(n - 1, -1, -1):
         kl = k % ROW
         if k >= ROW:
-            ins += sel("z1", "a1")
-            if k > ROW:
-                ins.append(fmac("a0", "a1", f"c0_{k}", kl))
-                ins.append(cmp((k - 1) % ROW))
-                ins.append(fmac("a1", "a1", f"c1_{k}", kl))
-            else:   # k = 16: no slot-1 update
-                ins.append(cmp((k - 1) % ROW))
-                ins.append(fmac("a0", "a1", f"c0_{k}", kl))
+            fmas = [fmac("a0", "a1", f"c0_{k}", kl)]
+            if k > ROW:       # k = 16: no slot-1 update
+                fmas.append(fmac("a1", "a1", f"c1_{k}", kl))
+            steps.append((kl, ("z1", "a1"), fmas))
         else:
-            ins += sel("z0", "a0")
-            if k >= 1:
-                ins.append(cmp((k - 1) % ROW))
-                ins.append(fmac("a0", "a0", f"c0_{k}", kl))
+            steps.append((kl, ("z0", "a0"), [fmac("a0", "a0", f"c0_{k}", kl)] if k >= 1 else []))
     uses = [f"c0_{k}" for k in range(1, n)] + [f"c1_{k}" for k in range(ROW + 1, n)]
-    return ins, uses
+    return solve(steps), uses
 
 
 def dot(n):
-    ins = ["s_nop 1"]
+    sc = Sched()
     for i in range(n):
         src = "x0" if i < ROW else "x1"
         acc = ("a", "b") if i % 2 == 0 else ("a2", "b2")
-        ins.append(fmac(acc[0], src, f"ma_{i}", i % ROW))
-        ins.append(fmac(acc[1], src, f"mb_{i}", i % ROW))
-    return ins
+        sc.emit(Ins(f"v_fmac_f64_dpp %[{acc[0]}], %[{src}], %[ma_{i}] row_newbcast:{i % ROW}{DPP}",
+                    w=[acc[0]], r=[acc[0], f"ma_{i}"], dpp=[src]))
+        sc.emit(Ins(f"v_fmac_f64_dpp %[{acc[1]}], %[{src}], %[mb_{i}] row_newbcast:{i % ROW}{DPP}",
+                    w=[acc[1]], r=[acc[1], f"mb_{i}"], dpp=[src]))
+    return sc.out
 
 
 def asm_text(ins):
@@ -109,9 +139,11 @@ def emit_solve(name, n, ins, uses, doc):
 template <>
 __device__ __forceinline__ void {name}<{n}>(const double (&c0)[{n}], const double (&c1)[{n}],
                                            double& a0, double& a1, double& z0, double& z1, int l) {{
+  unsigned long long m;   // the lane mask that takes turns with VCC
   asm volatile(
 {asm_text(ins)}
-      : [a0] "+{{v[0:1]}}"(a0), [a1] "+{{v[2:3]}}"(a1), [z0] "+{{v[4:5]}}"(z0), [z1] "+{{v[6:7]}}"(z1)
+      : [a0] "+{{v[0:1]}}"(a0), [a1] "+{{v[2:3]}}"(a1), [z0] "+{{v[4:5]}}"(z0), [z1] "+{{v[6:7]}}"(z1),
+        [m] "=&s"(m)
       : {ins_ops}
       : "vcc");
 }}
@@ -195,9 +227,13 @@ def r64(name):
 
 
 class Ins:
-    def __init__(self, text, w=(), r=(), dpp=(), trans=False, wvcc=False, rvcc=False):
+    def __init__(self, text, w=(), r=(), dpp=(), trans=False, wvcc=False, rvcc=False,
+                 wmask=(), rmask=()):
         self.text, self.w, self.r, self.dpp = text, set(w), set(r), set(dpp)
-        self.trans, self.wvcc, self.rvcc = trans, wvcc, rvcc
+        self.trans = trans
+        # lane masks written / read: "vcc" or the name of an SGPR-pair operand
+        self.wmask = set(wmask) | ({"vcc"} if wvcc else set())
+        self.rmask = set(rmask) | ({"vcc"} if rvcc else set())
 
 
 def ldl_prep(k, n):
@@ -221,7 +257,7 @@ def ldl_prep(k, n):
          Ins(f"ds_write_b64 %[addr], v[{D}:{D + 1}] offset:{8 * k}", r=["addr", "D"])]
     # scaling: the column the next multipliers come from goes through S (its halves), the other
     # in place; t1 = c1[k] itself while k < 16
-    if k < ROW - 1:          # t0 = keep_gt<k>(c0[k]), t1 = c1[k]
+    if k < ROW - 1:          # t0 = c0[k] on the lanes l > k, t1 = c1[k]
         p += [Ins(f"v_mul_f64 v[{Sr}:{Sr + 1}], -{r64('c0_' + str(k))}, v[{D}:{D + 1}]", w=[S], r=[f"c0_{k}", "D"]),
               Ins(f"v_mul_f64 {r64('c1_' + str(k))}, -{r64('c1_' + str(k))}, v[{D}:{D + 1}]", w=[f"c1_{k}"], r=[f"c1_{k}", "D"]),
               Ins(f"v_mov_b64 {r64('c0_' + str(k))}, v[{Sr}:{Sr + 1}]", w=[f"c0_{k}"], r=[S]),
@@ -231,7 +267,7 @@ def ldl_prep(k, n):
     elif k < ROW:            # k = 15: no slot-0 updates follow; t1 = c1[15]
         p += [Ins(f"v_mul_f64 {r64('c0_' + str(k))}, -{r64('c0_' + str(k))}, v[{D}:{D + 1}]", w=[f"c0_{k}"], r=[f"c0_{k}", "D"]),
               Ins(f"v_mul_f64 {r64('c1_' + str(k))}, -{r64('c1_' + str(k))}, v[{D}:{D + 1}]", w=[f"c1_{k}"], r=[f"c1_{k}", "D"])]
-    else:                    # t1 = keep_gt<k - 16>(c1[k])
+    else:                    # t1 = c1[k] on the lanes l > k - 16
         p += [Ins(f"v_mul_f64 {r64('c0_' + str(k))}, -{r64('c0_' + str(k))}, v[{D}:{D + 1}]", w=[f"c0_{k}"], r=[f"c0_{k}", "D"]),
               Ins(f"v_mul_f64 v[{Sr}:{Sr + 1}], -{r64('c1_' + str(k))}, v[{D}:{D + 1}]", w=[S], r=[f"c1_{k}", "D"]),
               Ins(f"v_mov_b64 {r64('c1_' + str(k))}, v[{Sr}:{Sr + 1}]", w=[f"c1_{k}"], r=[S]),
@@ -263,26 +299,39 @@ def ldl_upd(k, i):
                 w=[f"c1_{i}"], r=[f"c1_{i}", t1], dpp=[f"c1_{i}"])]
 
 
+class Entry:
+    """what ran ahead of the statement: a VALU instruction taken to have written every register and
+    mask (not a transcendental one: the whole-listing scan covers an operand that is)"""
+    trans = False
+
+    class _All:
+        def __and__(self, other):
+            return bool(other)
+        __rand__ = __and__
+    w = wmask = _All()
+
+
 class Sched:
     def __init__(self):
         self.out = []          # emitted texts
-        self.hist = []         # (Ins or None for nop slots) per issue slot
+        self.hist = [Entry()]  # (Ins or None for nop slots) per issue slot
 
     def need(self, ins):
-        """wait states still missing before ins can issue"""
+        """wait states still missing before ins can issue (the rule table's numbers)"""
         miss = 0
         for back, prev in enumerate(reversed(self.hist)):   # back = slots between prev and now
             if prev is None:
                 continue
-            if ins.dpp & prev.w and back < 2:
-                miss = max(miss, 2 - back)
-            if prev.trans and (ins.r | ins.dpp) & prev.w and back < 1:
-                miss = max(miss, 1 - back)
-            if prev.wvcc and ins.rvcc and back < 2:
-                miss = max(miss, 2 - back)
-            if back >= 2:
+            if ins.dpp & prev.w:
+                miss = max(miss, DPP_WAITS - back)
+            if prev.trans and not ins.trans and (ins.r | ins.dpp) & prev.w:
+                miss = max(miss, TRANS_WAITS - back)
+            for m in ins.rmask:
+                if prev.wmask & {m}:
+                    miss = max(miss, (VCC_WAITS if m == "vcc" else SGPR_WAITS) - back)
+            if back >= max(DPP_WAITS, TRANS_WAITS, VCC_WAITS, SGPR_WAITS):
                 break
-        return miss
+        return max(miss, 0)
 
     def emit(self, ins):
         m = self.need(ins)
